@@ -165,7 +165,14 @@ def parse_args():
                     help="after the timed region: the batch output of every distinct frame against the single-frame entry (checksums)")
     ap.add_argument("--host-io", type=int, default=1,
                     help="also time the SLR_MEM_HOST entry point (PCIe-inclusive, reported beside the result, never `value`)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (XYZ + mask of rank 0's / "
+                         "the contexts' frames) as DIR/xyz.npy, DIR/has.npy and DIR/pixel_index.npy; outputs of more than %d pixels "
+                         "are cut to a fixed seeded sample (see dump_outputs)" % DUMP_SAMPLE)
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _device_info(torch, index):
@@ -454,6 +461,36 @@ def self_spawn(args):
     raise SystemExit(subprocess.call(cmd, env=env))
 
 
+DUMP_SAMPLE = 1 << 20      # pixels --dump-outputs keeps of a larger output: 12 MB of XYZ + 4 MB of mask + 8 MB of indices
+
+
+def dump_outputs(out_dir, parts):
+    """--dump-outputs: the last timed step's results as the caller received them.  `parts` = [(xyz [..., 3] f32, has [...] u8)]
+    in frame order (one pair per context or per frame, on any device), taken as ONE sequence of pixels (frames x rows x cols).
+    Writes DIR/xyz.npy (float32 [n, 3]), DIR/has.npy (float32 [n]: the mask, or GRAY_ONLY's per-cell count) and
+    DIR/pixel_index.npy (float64 [n]: each pixel's flat index in that sequence).  Every pixel when there are at most DUMP_SAMPLE
+    of them, else a fixed sample of DUMP_SAMPLE (numpy default_rng(0), sorted): the same arguments give the same pixels."""
+    import numpy as np
+    import torch
+    sizes = [int(h.numel()) for _, h in parts]
+    total = sum(sizes)
+    if total <= DUMP_SAMPLE:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(total, DUMP_SAMPLE, replace=False)).astype(np.int64)
+    xs, hs, base = [], [], 0
+    for (x, h), n in zip(parts, sizes):
+        sel = idx[(idx >= base) & (idx < base + n)] - base
+        sel_t = torch.from_numpy(sel).to(h.device)
+        xs.append(x.reshape(-1, 3).index_select(0, sel_t).float().cpu().numpy())
+        hs.append(h.reshape(-1).index_select(0, sel_t).float().cpu().numpy())
+        base += n
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "xyz.npy"), np.concatenate(xs).astype(np.float32))
+    np.save(os.path.join(out_dir, "has.npy"), np.concatenate(hs).astype(np.float32))
+    np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+
+
 def hbm_footprint(torch, dev, items):
     """what one GPU holds for the job, by part (bytes), beside what the allocator and the driver report"""
     out = {k: int(v) for k, v in items.items()}
@@ -572,6 +609,8 @@ def main_one_process(args):
     sync_all()
     elapsed = time.perf_counter() - t0
     _trace("one-process: timed region done")
+    if args.dump_outputs:                                   # context k's frames are frames [k F, (k + 1) F) of the job
+        dump_outputs(args.dump_outputs, [(xyz_loc[k], has_loc[k]) for k in range(N)])
     prof = {}
     if args.profile:
         for c_ in ctxs:
@@ -705,6 +744,7 @@ def main_mfn(args):
     g_has = torch.zeros((F, world * band, W), dtype=torch.uint8, device=dev)
     ph = [torch.empty((max(rows, 1), W), dtype=torch.float32, device=dev) for _ in range(2)]
     vd = [torch.empty((max(rows, 1), W), dtype=torch.uint8, device=dev) for _ in range(2)]
+    last_out = [None] * F                                   # --dump-outputs: this rank's band of every frame, last step
 
     def step(i):
         for f in range(F):
@@ -714,6 +754,8 @@ def main_mfn(args):
                 ctx.mfn_rectify_decode(cam, stacks[f][cam], NF, NS, float(BLACK_THR), W=W, H=H, row0=r0, rows=rows,
                                        src_row0=win[cam][0], phase=ph[cam][:rows], valid=vd[cam][:rows])
             x, h, _ = ctx.mf_triangulate(ph[0][:rows], vd[0][:rows], ph[1][:rows], vd[1][:rows], want_match=False, row0=r0, image_h=H)
+            if args.dump_outputs:
+                last_out[f] = (x, h)
             if world > 1:                                   # (the band's place in the assembled frame; K4 has no output-view entry)
                 with torch.cuda.stream(ctx.stream):
                     g_xyz[f, rank * band:rank * band + rows].copy_(x, non_blocking=True)
@@ -738,6 +780,8 @@ def main_mfn(args):
         step(i)
     sync_all()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [p for p in last_out if p is not None])
     prof = ctx.profile()
     ctx.profile_enable(False)
     gather_ms, proof = None, None
@@ -1029,6 +1073,9 @@ def main():
     sync_all()
     elapsed = time.perf_counter() - t0
     _trace("timed region done")
+    if args.dump_outputs and rank == 0:                 # before any later leg reuses the output buffers
+        b = (args.steps - 1) % nbuf
+        dump_outputs(args.dump_outputs, [(xyz[b], has[b])])
     gather_ms, gather_proof = None, None
     if after_gather or final_gather or do_gather:
         b = (args.steps - 1) % nbuf

@@ -146,8 +146,8 @@ const char  *slr_last_error(const slr_ctx *ctx);
  * few waves as hold them; installed maps are digested again when the bit changes), bit 6 = straddling waves keep the three-row read
  * mode.  slr_mfn_rectify_decode (config 5): bit 0 = the per-pixel gather form, bit 1 = the register-staged tile form (as for the
  * u8 decodes: no digest / no buffer form), and two bits of its own: bit 7 = 512 threads x 2 pixels instead of 256 x 4 in the LDS-DMA
- * form, bit 8 = its ring of 4 plane groups (two workgroups per CU) instead of 3.  SLR_OPT_DEBUG_K4_STOP exists only
- * in -DSLR_DEBUG_HOOKS builds of the library (phase ablation of the match kernel; outputs are not written). */
+ * form, bit 8 = its ring of 4 plane groups (two workgroups per CU) instead of 3.  slr_fuse_voxels:
+ * bit 9 = count the insert pass's atomics (slr_fuse_last_stats).  SLR_OPT_DEBUG_K4_STOP exists only in -DSLR_DEBUG_HOOKS builds of the library (phase ablation of the match kernel; outputs are not written). */
 #define SLR_OPT_DEBUG_RECT_RESIDENT 8
 #define SLR_OPT_DEBUG_FLAGS 9
 #define SLR_OPT_DEBUG_K4_STOP 10
@@ -482,6 +482,45 @@ int slr_compact_points(slr_ctx *ctx, const float *xyz, const uint8_t *has, size_
 int slr_cloud_checksums(slr_ctx *ctx, int n_frames, int W, int H, const float *xyz, const uint8_t *has, uint64_t *out);
 int slr_verify_assembled(slr_ctx *const *ctxs, int n_ctx, int n_frames, int W, int H, float *const *xyz_all,
                          uint8_t *const *has_all, int *mismatches);
+
+/* ---- voxel-grid fusion of registered scans ----------------------------------------------------------------------------------
+ * The step the reference prepares and never takes: MFReconstruct::triangulation moves every scan after the first into the first
+ * scan's frame with scan/transfer_mat<sn>.txt "for stitching" (mfreconstruct.cpp:276-323), and MainWindow::startreconstruct then
+ * writes one <sn>.ply per scan (mainwindow.cpp:632-645).  slr_fuse_voxels merges n_frames organised clouds into ONE point per
+ * occupied cubic cell: the centroid of the cell's members, their count and (optionally) their mean grey value.
+ *   xyz [n_frames][H][W][3] f32, has [n_frames][H][W] u8 (non-zero = point), color [n_frames][H][W] u8 or NULL -- what
+ *   slr_reconstruct_mf_batch, _multi, _allgather_ex and slr_reconstruct_batch (SLR_MODE_GE, have_color) produce; n_frames H W < 2^32.
+ *   T [n_frames][12] f32 (a 3x4 row-major transform per frame, applied as MFReconstruct::triangulation applies transfer_mat: f64
+ *   accumulation, one narrowing to f32) or NULL.  T is ALWAYS a host array, like the plane-pointer arrays.
+ * Point e = (f H + i) W + j with has != 0: X = T[f] X (when T is given); a non-finite X is rejected; per axis a
+ *   g = ((double)X_a - origin_a) / voxel,  v_a = floor(g)  (outside [-2^20, 2^20): rejected),  q_a = (uint32)((g - v_a) 2^24).
+ * The cell (v_x, v_y, v_z) accumulates c = member count, S_a = sum of q_a (exact u64), first = smallest member e and the colour sum.
+ * Cells with c >= min_points are emitted IN ASCENDING ORDER OF first (order of first occurrence; deterministic, no sort), output m:
+ *   out_xyz[m][a] = (float)(origin_a + ((double)v_a + ((double)(S_a / c) + (double)(S_a % c) / (double)c) / 2^24) voxel)
+ *   out_count[m]  = c,   out_color[m] = (colour sum + c / 2) / c          (integer / and %; every operand exact in f64)
+ * *n_voxels = the number emitted, *n_rejected = the points rejected above; nothing at or past out_*[*n_voxels] is written.
+ * color and out_color are both NULL or both given.  max_voxels (1..2^30) is the output capacity: the context's hash table has a
+ * power of two >= 2 max_voxels entries of 48 B (scratch, kept until the context is destroyed).  More distinct voxels than
+ * max_voxels: SLR_ERR_OOM, nothing written to the outputs, *n_voxels = a count > max_voxels (a lower bound on the distinct voxels;
+ * the exact count unless the table filled up) -- retry with at least that capacity; *n_rejected = 0 then (the insert stops early,
+ * so the rejections are counted only on SLR_OK).
+ * Unlike slr_compact_points, n_voxels and n_rejected are ALWAYS host pointers and the call is synchronous whatever `mem` says (the
+ * distinct count decides between SLR_OK and SLR_ERR_OOM); xyz / has / color and the outputs follow `mem`.  Argument errors return
+ * SLR_ERR_INVALID_ARG with nothing enqueued.
+ * slr_fuse_last_stats: the last call's counters -- points (n_frames H W), distinct voxels, table entries, and the insert pass's
+ * global atomics (counted only while bit 9 (512) of SLR_OPT_DEBUG_FLAGS is set, else 0). */
+typedef struct slr_fuse_desc {
+    int n_frames, W, H;
+    double voxel;          /* cell edge, finite, > 0 (the clouds' unit: mm for the reference) */
+    double origin[3];      /* a corner of cell (0, 0, 0), finite */
+    uint32_t min_points;   /* >= 1 */
+    uint32_t max_voxels;   /* output capacity */
+} slr_fuse_desc;
+typedef struct slr_fuse_stats { uint64_t points, distinct, table_entries, atomics; } slr_fuse_stats;
+int slr_fuse_voxels(slr_ctx *ctx, const slr_fuse_desc *desc, const float *xyz, const uint8_t *has, const uint8_t *color,
+                    const float *T, float *out_xyz, uint32_t *out_count, uint8_t *out_color, uint32_t *n_voxels,
+                    uint64_t *n_rejected, slr_mem mem);
+int slr_fuse_last_stats(slr_ctx *ctx, slr_fuse_stats *out);
 
 /* page-locked host memory (the H2D / D2H copies of SLR_MEM_HOST calls are truly asynchronous only from / to it) */
 int slr_host_alloc(void **ptr, size_t bytes);

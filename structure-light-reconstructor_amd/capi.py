@@ -48,6 +48,7 @@ SYMBOLS = [
     "slr_ge_triangulate", "slr_ray_triangulate", "slr_line_line_intersections", "slr_pointcloud_from_grid", "slr_pointcloud_get",
     "slr_reconstruct_mf", "slr_reconstruct_ge", "slr_reconstruct_gray", "slr_reconstruct_mf_batch", "slr_reconstruct_batch", "slr_reconstruct_mf_cloud", "slr_reconstruct_mf_multi", "slr_reconstruct_mf_allgather", "slr_reconstruct_mf_allgather_ex", "slr_allgather_clouds", "slr_hybrid_rectify_decode_pair", "slr_reconstruct_hybrid_batch",
     "slr_prefix_index", "slr_compact_points", "slr_cloud_checksums", "slr_verify_assembled",
+    "slr_fuse_voxels", "slr_fuse_last_stats",
     "slr_host_alloc", "slr_host_free",
     "slr_timer_begin", "slr_timer_end", "slr_stream_copy", "slr_stream_mix", "slr_profile_enable", "slr_profile_reset",
     "slr_profile_kernel_count", "slr_profile_kernel_name", "slr_profile_get",
@@ -75,6 +76,17 @@ class RectifyInfo(C.Structure):
                 ("dma_tiles", C.c_uint), ("dma_nofit_tiles", C.c_uint), ("quads_by_class", C.c_uint * 3),
                 ("waves_by_mode", C.c_uint * 3), ("lds_nofit_tiles", C.c_uint * 2), ("dma_extra_entries", C.c_uint)]
 
+
+class FuseDesc(C.Structure):
+    _fields_ = [("n_frames", C.c_int), ("W", C.c_int), ("H", C.c_int), ("voxel", C.c_double), ("origin", C.c_double * 3),
+                ("min_points", C.c_uint32), ("max_voxels", C.c_uint32)]
+
+
+class FuseStats(C.Structure):
+    _fields_ = [("points", C.c_uint64), ("distinct", C.c_uint64), ("table_entries", C.c_uint64), ("atomics", C.c_uint64)]
+
+
+DEBUG_FUSE_COUNT_ATOMICS = 512  # SLR_OPT_DEBUG_FLAGS bit 9: slr_fuse_voxels counts its insert pass's atomics (fuse_last_stats)
 
 MODE_GRAY, MODE_GE, MODE_MF = 0, 1, 2
 ASSIGN_CYCLIC, ASSIGN_BLOCKED = 0, 1          # frame -> context assignment of the one-process multi-GPU entries (slr.h)
@@ -663,6 +675,60 @@ class Context:
         k = int(cnt[0]) & 0xFFFFFFFF
         return out[:k], src[:k]
 
+    def fuse_voxels(self, xyz, has, voxel, origin=(0.0, 0.0, 0.0), min_points=1, T=None, color=None, max_voxels=None):
+        """slr_fuse_voxels: one point per occupied cubic cell of edge `voxel` over every frame (include/slr.h has the exact rule)
+        -> (points [M][3] f32, counts [M] (u32 on the host; int64 on the device: torch has no full u32), grey values [M] u8 or None,
+        n_rejected).
+        xyz [H][W][3] or [n][H][W][3], has [H][W] or [n][H][W], color (optional) shaped like has: numpy arrays (host) or torch.cuda
+        tensors (device).  T: None or one 3x4 transform per frame ([n][3][4], [n][12]; [3][4] for one frame), host or torch.
+        max_voxels None: the capacity starts at min(points, 2^20) and grows to what the library reports when it does not suffice;
+        an explicit max_voxels that does not suffice raises SlrError(ERR_OOM) whose .n_voxels is the reported count."""
+        if tuple(has.shape[-2:]) != tuple(xyz.shape[-3:-1]) or xyz.shape[-1] != 3 or has.ndim not in (2, 3) or xyz.ndim != has.ndim + 1:
+            raise ValueError("xyz must be [n][H][W][3] (or [H][W][3]) and has [n][H][W] (or [H][W])")
+        n, H, W = (1,) + tuple(has.shape) if has.ndim == 2 else tuple(has.shape)
+        if color is not None and tuple(color.shape) != tuple(has.shape):
+            raise ValueError("color must be shaped like has")
+        mem = self._mem([xyz, has, color])
+        Th = None
+        if T is not None:
+            Tn = T.detach().cpu().numpy() if _is_torch(T) else np.asarray(T)
+            if Tn.size != 12 * n:
+                raise ValueError("T must hold one 3x4 transform per frame")
+            Th = np.ascontiguousarray(Tn, dtype=np.float32).reshape(n, 12)
+        npts = n * H * W
+        cap = int(max_voxels) if max_voxels is not None else max(1, min(npts, 1 << 20))
+        while True:
+            desc = FuseDesc(n, W, H, float(voxel), (C.c_double * 3)(*[float(o) for o in origin]), int(min_points), cap)
+            if mem == MEM_DEVICE:
+                import torch
+                out = self._new(mem, (cap, 3), np.float32, xyz)
+                cnt = self._new(mem, (cap,), np.int32, xyz)
+                col = self._new(mem, (cap,), np.uint8, xyz) if color is not None else None
+            else:
+                out, cnt = np.empty((cap, 3), np.float32), np.empty(cap, np.uint32)
+                col = np.empty(cap, np.uint8) if color is not None else None
+            nv, nrej = C.c_uint32(0), C.c_uint64(0)
+            st = self.lib.slr_fuse_voxels(self.h, C.byref(desc), _ptr(xyz), _ptr(has), _ptr(color), _ptr(Th), _ptr(out), _ptr(cnt),
+                                          _ptr(col), C.byref(nv), C.byref(nrej), C.c_int(mem))
+            if st == ERR_OOM and max_voxels is None and cap < min(npts, 1 << 30):
+                cap = min(npts, 1 << 30, max(2 * cap, nv.value))
+                continue
+            try:
+                self._chk(st)
+            except SlrError as e:
+                e.n_voxels = nv.value
+                raise
+            m = nv.value
+            counts = cnt[:m].to(torch.int64) & 0xFFFFFFFF if mem == MEM_DEVICE else cnt[:m]
+            return out[:m], counts, (col[:m] if col is not None else None), nrej.value
+
+    def fuse_last_stats(self):
+        """the last fuse_voxels call's counters: points, distinct voxels, table entries, insert atomics (counted only with
+        OPT_DEBUG_FLAGS bit DEBUG_FUSE_COUNT_ATOMICS set)"""
+        s = FuseStats()
+        self._chk(self.lib.slr_fuse_last_stats(self.h, C.byref(s)))
+        return {"points": s.points, "distinct": s.distinct, "table_entries": s.table_entries, "atomics": s.atomics}
+
     # -- measurement
     def cloud_checksums(self, xyz, has):
         """one 64-bit word per frame of a device-resident cloud xyz [n][H][W][3] / has [n][H][W]"""
@@ -770,6 +836,11 @@ def reconstruct_mf_multi(ctxs, stacks, black_thr, rectify, W=None, gather_ctx=0,
                                               _ptr(xa), _ptr(ha))
     ctxs[0]._chk(st)
     return (xa, ha) if gather_ctx >= 0 else (xyz, has)
+
+
+def fuse_voxels(ctx, xyz, has, voxel, **kw):
+    """Context.fuse_voxels on `ctx` (e.g. the context that holds an assembled cloud after allgather_clouds)"""
+    return ctx.fuse_voxels(xyz, has, voxel, **kw)
 
 
 def verify_assembled(ctxs, xyz_all, has_all):

@@ -102,22 +102,6 @@ __device__ __forceinline__ void reproject(const double *Q, int simple, double p0
     }
 }
 
-// matCoordTrans(3x4 f32) * [X;1]  (OpenCV f32 GEMM: f64 accumulate, narrow once)
-__device__ __forceinline__ void apply_T(const float *T, float X[3])
-{
-    float Y[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        double s = 0;
-        s += (double)T[r * 4 + 0] * (double)X[0];
-        s += (double)T[r * 4 + 1] * (double)X[1];
-        s += (double)T[r * 4 + 2] * (double)X[2];
-        s += (double)T[r * 4 + 3] * 1.0;
-        Y[r] = (float)s;
-    }
-    X[0] = Y[0]; X[1] = Y[1]; X[2] = Y[2];
-}
-
 // mfreconstruct.cpp:295 fabs(cam1Pix[0] - cam2Pix[0]) < 0.1.  Strict IEEE (default): the f32 difference is rounded before it
 // widens, and |d| < 0.1 (double) <=> |d| < 0.1f for a float d.  SLR_OPT_EVAL_MODEL = 1: the reference's x87 binary keeps the
 // difference of the two floats on the 53-bit stack (exact here) and hands it to fabs(double) unrounded.

@@ -23,7 +23,8 @@ const char *kKernelNames[K_COUNT] = {
     "slr_mf_match_triangulate", "slr_ge_match_triangulate", "slr_ray_count", "slr_ray_scan", "slr_ray_scatter",
     "slr_ray_triangulate",
     "slr_pc_from_grid", "slr_pc_get", "slr_undistort_table", "slr_ray_table", "slr_mf_rectify_decode_pair", "slr_mfn_decode",
-    "slr_gray_rectify_decode_pair", "slr_hybrid_rectify_decode_pair", "slr_mfn_rectify_decode"};
+    "slr_gray_rectify_decode_pair", "slr_hybrid_rectify_decode_pair", "slr_mfn_rectify_decode",
+    "slr_fuse_clear", "slr_fuse_insert", "slr_fuse_total", "slr_fuse_flag", "slr_fuse_scan", "slr_fuse_emit"};
 
 // scratch slots (device buffers owned by the ctx, grown on demand, reused across calls)
 enum Slot {
@@ -32,6 +33,7 @@ enum Slot {
     S_CODEX_L, S_CODEY_L, S_CODEX_R, S_CODEY_R,
     S_RAY_CELL, S_RAY_CELL2, S_RAY_RANK, S_RAY_CNT, S_RAY_OFFS, S_RAY_ITEMS, S_RAY_LIST, S_SCAN_TMP,
     S_XYZ, S_HAS, S_COLOR, S_UND_L, S_UND_R, S_RAYS_L, S_RAYS_R, S_FLAGSCAN, S_COMPACT, S_K4_DEFER,
+    S_FUSE_TABLE, S_FUSE_STATS, S_FUSE_FLAGS, S_FUSE_SRC, S_FUSE_T,
     S_COUNT
 };
 
@@ -95,6 +97,7 @@ struct slr_ctx {
     long prof_seen[K_COUNT] = {};
     int opt_profile_stride = 1;    // SLR_OPT_PROFILE_STRIDE
     hipEvent_t t0 = nullptr, t1 = nullptr;
+    slr_fuse_stats fuse_stats = {};  // the last slr_fuse_voxels call's counters (slr_fuse_last_stats)
 };
 
 namespace {
@@ -1626,6 +1629,92 @@ int slr_compact_points(slr_ctx *c, const float *xyz, const uint8_t *has, size_t 
     return st.finish();
 }
 
+// ---- voxel-grid fusion of registered scans (kernels_fuse.hip) ------------------------------------------------------------------------
+int slr_fuse_voxels(slr_ctx *c, const slr_fuse_desc *d, const float *xyz, const uint8_t *has, const uint8_t *color, const float *T,
+                    float *out_xyz, uint32_t *out_count, uint8_t *out_color, uint32_t *n_voxels, uint64_t *n_rejected, slr_mem mem)
+{
+    if (!c) return SLR_ERR_INVALID_ARG;
+    if (!d || !xyz || !has || !out_xyz || !out_count || !n_voxels || !n_rejected) return fail(c, SLR_ERR_INVALID_ARG, "null argument");
+    if ((color == nullptr) != (out_color == nullptr)) return fail(c, SLR_ERR_INVALID_ARG, "color and out_color must both be given or both be NULL");
+    if (mem != SLR_MEM_HOST && mem != SLR_MEM_DEVICE) return fail(c, SLR_ERR_INVALID_ARG, "bad memory kind");
+    if (d->n_frames < 1 || d->W < 1 || d->H < 1) return fail(c, SLR_ERR_INVALID_ARG, "n_frames, W and H must be >= 1");
+    const unsigned long long n = (unsigned long long)d->n_frames * (unsigned long long)d->W * (unsigned long long)d->H;
+    if (n >= (1ull << 32)) return fail(c, SLR_ERR_INVALID_ARG, "n_frames * H * W must be < 2^32");
+    if (!isfinite(d->voxel) || !(d->voxel > 0)) return fail(c, SLR_ERR_INVALID_ARG, "voxel must be finite and > 0");
+    for (int a = 0; a < 3; a++) if (!isfinite(d->origin[a])) return fail(c, SLR_ERR_INVALID_ARG, "origin must be finite");
+    if (d->min_points < 1) return fail(c, SLR_ERR_INVALID_ARG, "min_points must be >= 1");
+    if (d->max_voxels < 1 || d->max_voxels > (1u << 30)) return fail(c, SLR_ERR_INVALID_ARG, "max_voxels must be 1..2^30");
+    SLR_TRY(use_device(c));
+    Stage st(c, mem);
+    const void *dx, *dh, *dc;
+    SLR_TRY(st.in(xyz, n * 12, &dx)); SLR_TRY(st.in(has, n, &dh)); SLR_TRY(st.in(color, n, &dc));
+    FuseLaunch L{};
+    L.xyz = (const float *)dx; L.has = (const uint8_t *)dh; L.color = (const uint8_t *)dc;
+    L.n = n; L.frame_px = (unsigned)((unsigned long long)d->W * d->H);
+    L.voxel = d->voxel; L.origin[0] = d->origin[0]; L.origin[1] = d->origin[1]; L.origin[2] = d->origin[2];
+    L.max_voxels = d->max_voxels; L.min_points = d->min_points; L.count_atomics = c->debug.fuse_count_atomics;
+    if (T) {                                             // a host array, whatever `mem` says (like the plane-pointer arrays)
+        void *dT;
+        SLR_TRY(get_scratch(c, S_FUSE_T, sizeof(float) * 12 * (size_t)d->n_frames, &dT));
+        SLR_HIP(c, hipMemcpyAsync(dT, T, sizeof(float) * 12 * (size_t)d->n_frames, hipMemcpyHostToDevice, c->stream));
+        L.T = (const float *)dT;
+    }
+    void *tmp, *src, *flags;
+    SLR_TRY(get_scratch(c, S_FUSE_TABLE, fuse_table_bytes(d->max_voxels), &L.table));
+    SLR_TRY(get_scratch(c, S_FUSE_STATS, fuse_stats_bytes(), &L.stats));
+    SLR_TRY(get_scratch(c, S_FUSE_FLAGS, n, &flags));
+    SLR_TRY(get_scratch(c, S_FUSE_SRC, sizeof(uint32_t) * (size_t)d->max_voxels, &src));
+    SLR_TRY(get_scratch(c, S_FLAGSCAN, flag_scan_temp_bytes(n), &tmp));
+    L.flags = (uint8_t *)flags; L.src = (uint32_t *)src;
+    void *ox = out_xyz, *oc = out_count, *ocol = out_color;
+    if (mem == SLR_MEM_HOST) {                           // staged; only the n_voxels emitted entries are copied back below
+        SLR_TRY(get_scratch(c, S_STAGE0 + 8, 12 * (size_t)d->max_voxels, &ox));
+        SLR_TRY(get_scratch(c, S_STAGE0 + 9, 4 * (size_t)d->max_voxels, &oc));
+        if (out_color) SLR_TRY(get_scratch(c, S_STAGE0 + 10, d->max_voxels, &ocol));
+    }
+    L.out_xyz = (float *)ox; L.out_count = (uint32_t *)oc; L.out_color = (uint8_t *)ocol;
+    { ProfScope ps(c, K_FUSE_CLEAR, true); SLR_HIP(c, launch_fuse_voxels(L, FUSE_CLEAR, c->stream)); }
+    { ProfScope ps(c, K_FUSE_INSERT, true); SLR_HIP(c, launch_fuse_voxels(L, FUSE_INSERT, c->stream)); }
+    { ProfScope ps(c, K_FUSE_TOTAL, true); SLR_HIP(c, launch_fuse_voxels(L, FUSE_TOTAL, c->stream)); }
+    { ProfScope ps(c, K_FUSE_FLAG, true); SLR_HIP(c, launch_fuse_voxels(L, FUSE_FLAG, c->stream)); }
+    uint32_t *tot_dev = nullptr;
+    { ProfScope ps(c, K_FUSE_SCAN);
+      SLR_HIP(c, launch_flag_scan(L.flags, n, 1, 1, 0, 0u, 0u, nullptr, nullptr, nullptr, L.src, tmp, &tot_dev, c->stream)); }
+    L.total = tot_dev;
+    { ProfScope ps(c, K_FUSE_EMIT, true); SLR_HIP(c, launch_fuse_voxels(L, FUSE_EMIT, c->stream)); }
+    FuseTotals tot;
+    SLR_HIP(c, hipMemcpyAsync(&tot, (uint8_t *)L.stats + fuse_stats_bytes() - sizeof(FuseTotals), sizeof tot, hipMemcpyDeviceToHost, c->stream));
+    SLR_HIP(c, hipStreamSynchronize(c->stream));         // the distinct count decides between SLR_OK and SLR_ERR_OOM
+    c->fuse_stats.points = n;
+    c->fuse_stats.distinct = tot.ndist;
+    c->fuse_stats.atomics = tot.atomics;
+    c->fuse_stats.table_entries = fuse_table_entries(d->max_voxels);
+    if (tot.ndist > d->max_voxels || tot.abort) {
+        *n_rejected = 0;                                 // (the insert gave up early: its rejection count is partial)
+        *n_voxels = tot.ndist > d->max_voxels ? tot.ndist : d->max_voxels + 1;
+        char msg[160];
+        snprintf(msg, sizeof msg, "at least %u distinct voxels, more than max_voxels = %u (retry with a larger capacity)", tot.ndist,
+                 d->max_voxels);
+        return fail(c, SLR_ERR_OOM, "slr_fuse_voxels: output capacity exceeded", msg);
+    }
+    *n_voxels = tot.emitted;
+    *n_rejected = tot.rejected;
+    if (mem == SLR_MEM_HOST && tot.emitted) {
+        SLR_HIP(c, hipMemcpyAsync(out_xyz, ox, 12 * (size_t)tot.emitted, hipMemcpyDeviceToHost, c->stream));
+        SLR_HIP(c, hipMemcpyAsync(out_count, oc, 4 * (size_t)tot.emitted, hipMemcpyDeviceToHost, c->stream));
+        if (out_color) SLR_HIP(c, hipMemcpyAsync(out_color, ocol, tot.emitted, hipMemcpyDeviceToHost, c->stream));
+        SLR_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return SLR_OK;
+}
+
+int slr_fuse_last_stats(slr_ctx *c, slr_fuse_stats *out)
+{
+    if (!c || !out) return fail(c, SLR_ERR_INVALID_ARG, "null argument");
+    *out = c->fuse_stats;
+    return SLR_OK;
+}
+
 // ---- several GPUs in one process -------------------------------------------------------------------------------------------------
 // Frame f of the job runs on ctxs[f % n_ctx] (its shard index is f / n_ctx); every ctx works through its shard on its own
 // stream, so the devices run concurrently; afterwards the cloud is assembled by direct peer copies on the PRODUCING streams
@@ -2097,7 +2186,8 @@ int slr_set_option(slr_ctx *c, int option, int value)
             c->debug.rect_resident = value;
             return SLR_OK;
         case SLR_OPT_DEBUG_FLAGS:
-            if (value < 0 || value > 511) return fail(c, SLR_ERR_INVALID_ARG, "SLR_OPT_DEBUG_FLAGS must be 0..511");
+            if (value < 0 || value > 1023) return fail(c, SLR_ERR_INVALID_ARG, "SLR_OPT_DEBUG_FLAGS must be 0..1023");
+            c->debug.fuse_count_atomics = (value & 512) != 0;
             c->debug.mfn_nt512 = (value & 128) != 0;
             c->debug.mfn_ring4 = (value & 256) != 0;
             c->debug.no_tiled_map = (value & 1) != 0;

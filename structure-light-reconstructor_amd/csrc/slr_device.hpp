@@ -48,7 +48,8 @@ struct DevCalib {
 // kernel ids for the built-in HIP-event profiler (bench.py reads these)
 enum KernelId {
     K_REMAP = 0, K_MF_DECODE, K_MF_RECT_DECODE, K_GRAY_DECODE, K_GRAY_RECT_DECODE,
-    K_MF_MATCH, K_GE_MATCH, K_RAY_COUNT, K_RAY_SCAN, K_RAY_SCATTER, K_RAY_TRI, K_PC_FROM_GRID, K_PC_GET, K_UNDISTORT_TABLE, K_RAY_TABLE, K_MF_RECT_DECODE_PAIR, K_MFN_DECODE, K_GRAY_RECT_DECODE_PAIR, K_HYBRID_RECT_DECODE_PAIR, K_MFN_RECT_DECODE, K_COUNT
+    K_MF_MATCH, K_GE_MATCH, K_RAY_COUNT, K_RAY_SCAN, K_RAY_SCATTER, K_RAY_TRI, K_PC_FROM_GRID, K_PC_GET, K_UNDISTORT_TABLE, K_RAY_TABLE, K_MF_RECT_DECODE_PAIR, K_MFN_DECODE, K_GRAY_RECT_DECODE_PAIR, K_HYBRID_RECT_DECODE_PAIR, K_MFN_RECT_DECODE,
+    K_FUSE_CLEAR, K_FUSE_INSERT, K_FUSE_TOTAL, K_FUSE_FLAG, K_FUSE_SCAN, K_FUSE_EMIT, K_COUNT
 };
 
 // Every kernel launch goes through SLR_LAUNCH.  When the C-ABI layer's profiler has armed a pair of events for the
@@ -74,6 +75,7 @@ struct DebugKnobs {
     bool mfn_ring4 = false;      // config 5, LDS-DMA rectified decode: a ring of 4 plane groups (two workgroups per CU) instead of 3
     int k4_stop = 0;
     bool poison_scratch = false; // SLR_OPT_DEBUG_POISON_SCRATCH
+    bool fuse_count_atomics = false; // slr_fuse_voxels: count the insert pass's atomics (slr_fuse_last_stats)
     bool eval_x87 = false;       // SLR_OPT_EVAL_MODEL = 1 (not a debug knob, but it travels the same way: per call, per thread)
 };
 extern thread_local DebugKnobs tl_debug;
@@ -232,12 +234,49 @@ hipError_t launch_flag_scan(const uint8_t *flags, size_t n, int w, int h, int co
                             uint32_t *index, const float *xyz, float *out_xyz, uint32_t *out_src, void *temp,
                             uint32_t **total_dev, hipStream_t s);
 
+// voxel-grid fusion (kernels_fuse.hip, slr_fuse_voxels).  table: fuse_table_bytes(max_voxels); stats: fuse_stats_bytes() -- the
+// counter shards, then FuseTotals (read back by the host after FUSE_EMIT); flags: n bytes; src: max_voxels u32; total: the flag
+// scan's device count.  One launch per phase, in this order, with the flag scan (launch_flag_scan) between FUSE_FLAG and FUSE_EMIT.
+struct FuseTotals { unsigned long long rejected, atomics; unsigned ndist, abort, emitted, pad; };
+enum FusePhase { FUSE_CLEAR = 0, FUSE_INSERT, FUSE_TOTAL, FUSE_FLAG, FUSE_EMIT };
+struct FuseLaunch {
+    const float *xyz; const uint8_t *has; const uint8_t *color; const float *T /* [n_frames][12] on the device, or null */;
+    size_t n; unsigned frame_px;
+    double voxel, origin[3];
+    uint32_t max_voxels, min_points;
+    int count_atomics;                   // debug: count the insert's atomics into FuseTotals::atomics
+    void *table, *stats;
+    uint8_t *flags; uint32_t *src; const uint32_t *total;
+    float *out_xyz; uint32_t *out_count; uint8_t *out_color;
+};
+size_t     fuse_table_entries(uint32_t max_voxels);
+size_t     fuse_table_bytes(uint32_t max_voxels);
+size_t     fuse_stats_bytes();
+hipError_t launch_fuse_voxels(const FuseLaunch &L, int phase, hipStream_t s);
+
 hipError_t launch_pc_from_grid(const float *xyz, const uint8_t *has, const uint8_t *color, int W, int H,
                                int scan_w, int scan_h, float *pc_sum, uint8_t *pc_count, uint8_t *pc_color,
                                hipStream_t s);
 hipError_t launch_pc_get(const float *pc_sum, const uint8_t *pc_count, size_t n, float *out, hipStream_t s);
 
 #if defined(__HIPCC__)
+// matCoordTrans(3x4 f32) * [X;1]  (OpenCV f32 GEMM: f64 accumulate, narrow once) -- the scan-to-scan transfer of
+// MFReconstruct::triangulation (kernels_match.hip) and the per-frame transforms of the voxel fusion (kernels_fuse.hip)
+__device__ __forceinline__ void apply_T(const float *T, float X[3])
+{
+    float Y[3];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        double s = 0;
+        s += (double)T[r * 4 + 0] * (double)X[0];
+        s += (double)T[r * 4 + 1] * (double)X[1];
+        s += (double)T[r * 4 + 2] * (double)X[2];
+        s += (double)T[r * 4 + 3] * 1.0;
+        Y[r] = (float)s;
+    }
+    X[0] = Y[0]; X[1] = Y[1]; X[2] = Y[2];
+}
+
 // Exclusive scan over a workgroup of BLOCK threads (the lean match kernels' index build, K6's bucket places): every wave scans itself with DPP lane
 // shifts (row_shr 1 / 2 / 4 / 8, then row_bcast 15 and 31: six VALU steps, no LDS crossbar), the (at most 16) wave totals cross in
 // LDS behind ONE barrier and every wave scans them for itself -- in place of hipcub::BlockScan, whose warp-scans form spends two

@@ -230,4 +230,8 @@ private:
     int w, h;
 };
 
+// The fused cloud of a scan series (slr_fuse_voxels): an ASCII PLY of m vertices "x y z" in the mesh writer's number format (%g),
+// no faces -- what the reference's PlyLoader reads.  false: the file cannot be written.
+bool writePointsPly(const std::string &path, const float *xyz, size_t m);
+
 }  // namespace duke

@@ -2,6 +2,7 @@
 // the body of slr_cli.  duke_run_project mirrors MainWindow::startreconstruct (Duke/mainwindow.cpp:562-652).
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <memory>
 #include <mutex>
@@ -331,6 +332,72 @@ void duke_pointcloud_accumulate(int w, int h, const float *pts, int n, float *su
             float *m = mean + ((size_t)j * w + i) * 3;
             m[0] = ok ? p.x : 0; m[1] = ok ? p.y : 0; m[2] = ok ? p.z : 0;
         }
+}
+
+// The series above (one pipeline, or several GPUs with n_devices > 0) and then ONE model of it: the per-scan PointCloudImage clouds,
+// each already moved into the first scan's frame by its transfer_mat (mfreconstruct.cpp:276-323), fused by slr_fuse_voxels (cell
+// edge `voxel`, cells of at least min_points members) on the calling thread's current device.  A cell's point is sum / count as
+// slr_pointcloud_get forms it (PointCloudImage::getPoint); no transform is passed.  Writes fused_ply (writePointsPly) and the
+// per-scan meshes under ply_prefix as duke_run_series does.  pc_sum / pc_count may be NULL (else they receive the scans' clouds),
+// out_xyz may be NULL (else capacity n_scans scan_w scan_h points); *n_voxels (may be NULL) = the fused point count.
+// Returns 1 on success, 0 on failure (err says why).
+int duke_fuse_series(const char *project, int sn_first, int n_scans, int scan_w, int scan_h, int cam_w, int cam_h, int black_thr,
+                     int white_thr, const char *suffix, const char *ply_prefix, const int *devices, int n_devices, double voxel,
+                     unsigned min_points, const char *fused_ply, float *pc_sum, uint8_t *pc_count, float *out_xyz, uint32_t *n_voxels,
+                     char *err, int err_len)
+{
+    DUKE_GUARD_BEGIN
+    if (!project || !fused_ply || n_scans < 1 || scan_w <= 0 || scan_h <= 0 || !(voxel > 0) || min_points < 1) {
+        set_err(err, err_len, "bad argument");
+        return 0;
+    }
+    const size_t cells = (size_t)scan_w * scan_h, n = cells * (size_t)n_scans;
+    if (n >= (1ull << 32)) { set_err(err, err_len, "n_scans * scan_w * scan_h must be < 2^32"); return 0; }
+    std::vector<float> sum_own, pts(n * 3);
+    std::vector<uint8_t> cnt_own, has(n);
+    if (!pc_sum) { sum_own.resize(n * 3); pc_sum = sum_own.data(); }
+    if (!pc_count) { cnt_own.resize(n); pc_count = cnt_own.data(); }
+    const int done = n_devices > 0
+        ? duke_run_series_multi(project, sn_first, n_scans, scan_w, scan_h, cam_w, cam_h, black_thr, white_thr, suffix, ply_prefix, devices,
+                                n_devices, pc_sum, pc_count, err, err_len)
+        : duke_run_series(project, sn_first, n_scans, scan_w, scan_h, cam_w, cam_h, black_thr, white_thr, suffix, ply_prefix, pc_sum,
+                          pc_count, err, err_len);
+    if (done != n_scans) return 0;
+    int dev = 0;
+    slr_ctx *ctx = nullptr;
+    if (slr_current_device(&dev) != SLR_OK || slr_create(dev, &ctx) != SLR_OK) { set_err(err, err_len, "no GPU for the fusion"); return 0; }
+    std::unique_ptr<slr_ctx, int (*)(slr_ctx *)> own(ctx, slr_destroy);
+    if (slr_pointcloud_get(ctx, pc_sum, pc_count, n, pts.data(), SLR_MEM_HOST) != SLR_OK) {
+        set_err(err, err_len, std::string("slr_pointcloud_get: ") + slr_last_error(ctx));
+        return 0;
+    }
+    for (size_t k = 0; k < n; k++) has[k] = pc_count[k] != 0;
+    slr_fuse_desc d = {};
+    d.n_frames = n_scans; d.W = scan_w; d.H = scan_h; d.voxel = voxel; d.min_points = min_points;
+    uint32_t cap = (uint32_t)(n < (1u << 22) ? n : (1u << 22)), m = 0;
+    std::vector<float> fused;
+    std::vector<uint32_t> count;
+    for (;;) {                                           // capacity grown to the reported count on SLR_ERR_OOM
+        fused.resize((size_t)cap * 3); count.resize(cap);
+        d.max_voxels = cap;
+        uint64_t rejected = 0;
+        const int st = slr_fuse_voxels(ctx, &d, pts.data(), has.data(), nullptr, nullptr, fused.data(), count.data(), nullptr, &m,
+                                       &rejected, SLR_MEM_HOST);
+        if (st == SLR_OK) break;
+        if (st == SLR_ERR_OOM && cap < n && cap < (1u << 30)) {
+            const size_t want = std::max<size_t>((size_t)cap * 2, m);
+            cap = (uint32_t)std::min<size_t>(std::min<size_t>(want, n), (size_t)1 << 30);
+            continue;
+        }
+        set_err(err, err_len, std::string("slr_fuse_voxels: ") + slr_last_error(ctx));
+        return 0;
+    }
+    if (out_xyz) memcpy(out_xyz, fused.data(), (size_t)m * 12);
+    if (n_voxels) *n_voxels = m;
+    if (!writePointsPly(fused_ply, fused.data(), m)) { set_err(err, err_len, std::string("cannot write ") + fused_ply); return 0; }
+    set_err(err, err_len, "");
+    return 1;
+    DUKE_GUARD_END(0, err, err_len)
 }
 
 }  // extern "C"

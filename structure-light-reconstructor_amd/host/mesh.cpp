@@ -126,4 +126,18 @@ bool MeshCreator::exportObjMesh(const std::string &path)
     return (bool)out;
 }
 
+bool writePointsPly(const std::string &path, const float *xyz, size_t m)
+{
+    std::string s;
+    s.reserve(64 + m * 36);
+    s += "ply\nformat ascii 1.0\nelement vertex "; put(s, (unsigned)m);
+    s += "\nproperty float x\nproperty float y\nproperty float z\nend_header\n";
+    for (size_t k = 0; k < m; k++) {
+        put(s, xyz[3 * k]); s += ' '; put(s, xyz[3 * k + 1]); s += ' '; put(s, xyz[3 * k + 2]); s += '\n';
+    }
+    std::ofstream out(path.c_str(), std::ios::binary);
+    out.write(s.data(), (std::streamsize)s.size());
+    return (bool)out;
+}
+
 }  // namespace duke

@@ -3,6 +3,8 @@
 //   slr_cli <project> <mode: gray|grayepi|mf> [--sn N] [--scan W H] [--cam W H] [--black T] [--white T] [--color] [--suffix .png|.pgm]
 //           [--series K]   (mf only: scans N .. N+K-1, pipelined: PNG decode of the next scan overlaps the GPU work of this one)
 //           [--devices 0,1,..]   (with --series: the scans are dealt round-robin to these GPUs, one pipeline per entry)
+//           [--fuse VOXEL [--min-points N]]   (with --series: the scans' clouds also fused into ONE cloud of cells of edge VOXEL,
+//                                              cells of at least N points (default 1): <project>/reconstruction/fused.ply)
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -11,6 +13,8 @@
 
 extern "C" int duke_run_project(const char *, int, int, int, int, int, int, int, int, int, const char *, const char *, float *,
                                 unsigned char *, unsigned char *, char *, int);
+extern "C" int duke_fuse_series(const char *, int, int, int, int, int, int, int, int, const char *, const char *, const int *, int, double,
+                                 unsigned, const char *, float *, uint8_t *, float *, uint32_t *, char *, int);
 extern "C" int duke_run_series(const char *, int, int, int, int, int, int, int, int, const char *, const char *, float *,
                                unsigned char *, char *, int);
 extern "C" int duke_run_series_multi(const char *, int, int, int, int, int, int, int, int, const char *, const char *, const int *, int,
@@ -26,6 +30,8 @@ int main(int argc, char **argv)
     const int mode = m == "gray" ? 0 : m == "grayepi" ? 1 : 2;
     // defaults: Duke/Set.ui (scan 1280x1024, camera 1280x1024, blackThreshold 40, whiteThreshold 0)
     int sn = 0, sw = 1280, sh = 1024, cw = 1280, chh = 1024, black = 40, white = 0, color = 0, series = 0;
+    double fuse = 0;
+    unsigned min_points = 1;
     std::string suffix = ".png";
     int devices[64], n_devices = 0;
     for (int i = 3; i < argc; i++) {
@@ -36,12 +42,28 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--white") && i + 1 < argc) white = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--color")) color = 1;
         else if (!strcmp(argv[i], "--series") && i + 1 < argc) series = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--fuse") && i + 1 < argc) fuse = atof(argv[++i]);
+        else if (!strcmp(argv[i], "--min-points") && i + 1 < argc) min_points = (unsigned)atoi(argv[++i]);
         else if (!strcmp(argv[i], "--suffix") && i + 1 < argc) suffix = argv[++i];
         else if (!strcmp(argv[i], "--devices") && i + 1 < argc) {
             for (char *tok = strtok(argv[++i], ","); tok && n_devices < 64; tok = strtok(NULL, ",")) devices[n_devices++] = atoi(tok);
         }
     }
     char err[512] = "";
+    if (fuse != 0 && (series <= 0 || mode != 2 || !(fuse > 0) || min_points < 1)) {
+        fprintf(stderr, "--fuse VOXEL (> 0) needs mf --series K, and --min-points N >= 1\n");
+        return 2;
+    }
+    if (series > 0 && mode == 2 && fuse > 0) {
+        const std::string pre = project + "/reconstruction/", fused = pre + "fused.ply";
+        uint32_t m = 0;
+        const int ok = duke_fuse_series(project.c_str(), sn, series, sw, sh, cw, chh, black, white, suffix.c_str(), pre.c_str(),
+                                        n_devices > 0 ? devices : NULL, n_devices, fuse, min_points, fused.c_str(), NULL, NULL, NULL, &m,
+                                        err, (int)sizeof err);
+        if (!ok) { fprintf(stderr, "fused series failed: %s\n", err); return 1; }
+        printf("wrote %d meshes to %s<sn>.ply and %u fused points to %s\n", series, pre.c_str(), m, fused.c_str());
+        return 0;
+    }
     if (series > 0 && mode == 2) {
         const std::string pre = project + "/reconstruction/";
         const int done = n_devices > 0

@@ -86,18 +86,14 @@ int          slr_set_stream(slr_ctx *ctx, void *hip_stream);     /* borrow a cal
 int          slr_synchronize(slr_ctx *ctx);
 const char  *slr_last_error(const slr_ctx *ctx);
 /* tuning / test knobs.  SLR_OPT_MF_MATCH_ALGO: 0 = auto, 1 = linear LDS sweep (the literal form of
- * mfreconstruct.cpp:289-331), 2 = indexed exact form built by an LDS radix sort (distinct phases), 3 = indexed exact form
+ * mfreconstruct.cpp:289-331), 2 = retired (SLR_ERR_UNSUPPORTED), 3 = indexed exact form
  * built by an LDS counting sort (rows wider than 4096 pixels are matched against the right row in chunks of 4096 columns, up to
  * 32768 pixels; wider rows take the sweep).  0 picks 3, in its lean variant (same index, fewer instructions) when the rows are
- * aligned, 513..1024 or 2049..4096 pixels wide and Q has cv::stereoRectify's pattern.  4 / 5 / 6 pin the lean variant's
- * shapes for rows of 2049..4096 pixels (0 picks 1024 threads x 4 pixels with the row's XYZ stored through LDS; 4 = the same
- * with per-thread stores, round 2; 5 / 6 = 512 threads x 8 pixels with two / three rows per CU: measured, not faster, `make FORMS=all` builds only)
- * and behave as 0 where the lean variant does not apply; 7 = the grouped launches of slr_reconstruct_mf_batch as a persistent kernel
- * with the next row's phases prefetched (round 5: measured slower, 105 against 77 us per frame; `make FORMS=all` builds only); 8 = 0's
- * lean kernel by name (its index dedups equal right phases through an LDS hash table); 9 = the same index WITHOUT the dedup, rows with
- * an overfull bin rebuilt with it inside the kernel (round 6: measured slower on the reference's phases, 90 against 81 us -- its
- * integer-quotient atan leaves ~1500 distinct values in a row of 4064 valid pixels; `make FORMS=all` builds only).  All give identical
- * results. */
+ * aligned, 513..1024 or 2049..4096 pixels wide and Q has cv::stereoRectify's pattern.  4 pins the lean variant's
+ * shape for rows of 2049..4096 pixels (0 picks 1024 threads x 4 pixels with the row's XYZ stored through LDS; 4 = the same
+ * with per-thread stores, round 2) and behaves as 0 where the lean variant does not apply; 5, 6, 7 = retired (SLR_ERR_UNSUPPORTED);
+ * 8 = 0's lean kernel by name (its index dedups equal right phases through an LDS hash table); 9 = retired (SLR_ERR_UNSUPPORTED).
+ * All give identical results. */
 #define SLR_OPT_MF_MATCH_ALGO 1
 /* SLR_OPT_MF_DECODE_VEC: pixels per thread of the unfused K2 kernel: 0 = auto, 4, 8 or 16 (identical results) */
 #define SLR_OPT_MF_DECODE_VEC 2
@@ -106,10 +102,7 @@ const char  *slr_last_error(const slr_ctx *ctx);
  * source box does not fit their LDS budget.
  *   0 = auto (default): 7 when it applies, else 5, or 6 when the maps would make more pixels fall back in 5 than in 6
  *   1 = direct gather (no LDS tiles)
- *   2 = 64x16 tiles, two prefetch rounds
- *   3 = 64x8 tiles walking down tile columns with a 16-row sliding LDS window (no halo re-reads: 1.03x instead of
- *       1.13x the algorithmic HBM bytes, but ~3 % slower)
- *   4 = 128x8 tiles, 256 threads, two prefetch rounds
+ *   2, 3, 4 = retired (SLR_ERR_UNSUPPORTED)
  *   5 = 128x8 tiles, 512 threads (waves 0-3 left half, 4-7 right half), one round, pre-digested 4-byte map entries
  *   6 = 64x8 tiles, 256 threads, one round, pre-digested 4-byte map entries
  *   7 = LDS-DMA form (round 2): 256- or 128-pixel-wide tiles (SLR_OPT_RECT_DMA_SHAPE) decoded in 7 phases of two
@@ -117,7 +110,8 @@ const char  *slr_last_error(const slr_ctx *ctx);
  *       of a camera equally spaced in one allocation, 16-byte aligned rows, W % 16 == 0 and maps at least three quarters
  *       of whose tile boxes fit (the other tiles are rewritten by a gather pass behind the main kernel);
  *       auto falls back to 5 / 6 otherwise (also per call); an explicit 7 makes such calls fail with SLR_ERR_UNSUPPORTED.
- * The Gray fused decode only distinguishes 1 (gather), 2 (64x4 tiles) and everything else (64x8 tiles when they fit). */
+ * The Gray fused decode only distinguishes 1 (gather) and everything else (64x8 tiles when they fit, else 64x4 tiles;
+ * SLR_OPT_DEBUG_FLAGS bit 4 forces 64x4). */
 #define SLR_OPT_RECT_DECODE_ALGO 3
 /* SLR_OPT_ASYNC_HOST: 1 = calls with SLR_MEM_HOST buffers return once the H2D copies, the kernels and the D2H copies
  * are ENQUEUED on the ctx stream; outputs are valid (and inputs reusable) only after slr_synchronize(ctx).  The host
@@ -127,13 +121,12 @@ const char  *slr_last_error(const slr_ctx *ctx);
 #define SLR_OPT_ASYNC_HOST 4
 /* SLR_OPT_PROFILE_STRIDE: the built-in HIP-event profiler brackets every n-th launch of a kernel (default 1 = all) */
 #define SLR_OPT_PROFILE_STRIDE 5
-/* SLR_OPT_RECT_DMA_SHAPE: destination tile / workgroup size of form 7: 0 = 256x16 / 512 threads, 1 = 256x8 / 512, 2 = 256x8 / 256,
- * 3 = 128x16 / 512 (default), 4 = 128x8 / 256, 5 = 256x4 / 256, 6 = 128x16 / 256 (identical results; the tile tables of the installed maps
- * are rebuilt).  SLR_OPT_RECT_DMA_DEPTH: phases of LDS-DMA in flight ahead of
+/* SLR_OPT_RECT_DMA_SHAPE: destination tile / workgroup size of form 7: 0 = 256x16 / 512 threads, 1 = 256x8 / 512,
+ * 2 = retired (SLR_ERR_UNSUPPORTED), 3 = 128x16 / 512 (default), 4, 5, 6 = retired (SLR_ERR_UNSUPPORTED) (identical results; the
+ * tile tables of the installed maps are rebuilt).  SLR_OPT_RECT_DMA_DEPTH: phases of LDS-DMA in flight ahead of
  * the decode, 1 (double buffer) or 2 (triple buffer, the default).  Under SLR_OPT_EVAL_MODEL = 1 the multi-frequency decode exists at
  * distance 2 only: the option is ignored there and slr_get_rectify_info reports the effective value (2). */
-/* Forms that lost their measurements -- SLR_OPT_RECT_DECODE_ALGO 2, 3, 4, SLR_OPT_RECT_DMA_SHAPE 2, 4, 5, 6, SLR_OPT_MF_MATCH_ALGO 2, 5, 6, 7, 9
- * -- are compiled into the library with `make FORMS=all` only; a default build answers SLR_ERR_UNSUPPORTED to these values. */
+/* Retired values pass the range checks, return SLR_ERR_UNSUPPORTED and leave the option at its previous value. */
 #define SLR_OPT_RECT_DMA_SHAPE 6
 #define SLR_OPT_RECT_DMA_DEPTH 7
 /* Test knobs (results never change).  SLR_OPT_DEBUG_RECT_RESIDENT: n > 0 = run the persistent fused decodes on n workgroups

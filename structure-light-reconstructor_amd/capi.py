@@ -15,12 +15,11 @@ LIB_PATH = os.path.join(_HERE, "libslr_hip.so")
 MF_PLANES = 14
 MAX_GRAY_BITS = 16
 MEM_HOST, MEM_DEVICE = 0, 1
-OPT_MF_MATCH_ALGO = 1          # 0 auto, 1 linear sweep, 2 indexed (radix-sorted distinct phases), 3 indexed (counting sort), 4/5/6 lean shapes (1024x4, 512x8 two rows per CU, 512x8 three rows per CU), 7 persistent grouped K4 (FORMS=all builds only), 8 = the lean kernel auto picks, 9 = its index without the hash dedup (FORMS=all builds only)
-OPT_RECT_DECODE_ALGO = 3       # fused rectify+decode: 0 auto (5, else 6), 1 direct gather, 2 LDS tiles 64x16, 3 sliding LDS
-                               # window down tile columns, 4 tiles 128x8 / 256 threads, 5 tiles 128x8 / 512 threads,
-                               # 6 tiles 64x8 / 256 threads
-OPT_RECT_DMA_SHAPE = 6         # tile / threads of form 7 (LDS-DMA fused decode): 0 = 256x16/512, 1 = 256x8/512, 2 = 256x8/256,
-                               # 3 = 128x16/512, 4 = 128x8/256, 5 = 256x4/256, 6 = 128x16/256
+OPT_MF_MATCH_ALGO = 1          # 0 auto, 1 linear sweep, 2 retired (SLR_ERR_UNSUPPORTED), 3 indexed (counting sort), 4 lean 1024x4 with per-thread stores, 5/6/7 retired (SLR_ERR_UNSUPPORTED), 8 = the lean kernel auto picks, 9 retired (SLR_ERR_UNSUPPORTED)
+OPT_RECT_DECODE_ALGO = 3       # fused rectify+decode: 0 auto (5, else 6), 1 direct gather, 2/3/4 retired (SLR_ERR_UNSUPPORTED),
+                               # 5 tiles 128x8 / 512 threads, 6 tiles 64x8 / 256 threads
+OPT_RECT_DMA_SHAPE = 6         # tile / threads of form 7 (LDS-DMA fused decode): 0 = 256x16/512, 1 = 256x8/512, 2 retired (SLR_ERR_UNSUPPORTED),
+                               # 3 = 128x16/512, 4/5/6 retired (SLR_ERR_UNSUPPORTED)
 OPT_RECT_DMA_DEPTH = 7         # phases of LDS-DMA in flight ahead of the decode: 1 or 2
 OPT_DEBUG_RECT_RESIDENT = 8    # tests: workgroups of the persistent fused decodes (0 = resident set)
 OPT_DEBUG_FLAGS = 9            # tests: bit 0 no map digest, bit 1 no buffer-descriptor form, bit 2 no lean K5, bit 3 no fused decode+count

@@ -6,13 +6,11 @@
 // quotient is an integer) and the bilinear blend uses v_perm / v_dot2, which took K2 to the box's copy
 // ceiling.  The fused rectify+decode forms (SLR_OPT_RECT_DECODE_ALGO, include/slr.h) are bound by how the memory
 // system serves the short source row segments of a tile (profiles/exp/boxread.hip):
-//   mf_rect_decode_lds_kernel<TH, ROUNDS, STRIDED, TWV, PACKED, NT>   persistent workgroups, register prefetch pipeline
-//       <8,1,*,2,true,512>  128x8 tiles, 512 threads, map digest   (5, what "auto" picks when the maps fit it)
-//       <8,1,*,1,true,256>  64x8 tiles, map digest                 (6)
-//       <16,2,*>            64x16 tiles, two prefetch rounds       (2)
-//       <8,2,*,2>           128x8 tiles, 256 threads, two rounds   (4)
-//   mf_rect_decode_ring_kernel                                      16-row sliding LDS window down tile columns (3)
-//   mf_rect_decode_kernel<V>                                        direct gather (1, and the per-tile fallback)
+//   mf_rect_decode_lds_kernel<STRIDED, TWV, PACKED, NT>   persistent workgroups, register prefetch pipeline
+//       <*,2,true,512>  128x8 tiles, 512 threads, map digest   (5, what "auto" picks when the maps fit it)
+//       <*,1,true,256>  64x8 tiles, map digest                 (6)
+//       <*,1,false,256> 64x8 tiles, the caller's map           (6 with SLR_OPT_DEBUG_FLAGS bit 0)
+//   mf_rect_decode_kernel<V>                                direct gather (1, and the per-tile fallback)
 //
 // Reference behaviour restated (never copied):
 //   K1  stereoRect::doStereoRectify -> cv::remap(CV_16SC2,CV_16UC1,INTER_LINEAR)   Duke/stereorect.cpp:26-34
@@ -356,8 +354,8 @@ hipError_t launch_init_rectify_map(const double M[9], const double D[5], const d
 }
 
 // ------------------------------------------------------------------------------------------------------
-// fused K1+K2, LDS-tiled form (the default): a workgroup rectifies + decodes 64 x 8 destination tiles (64 x 16 with
-// SLR_OPT_RECT_DECODE_ALGO = 2), one pixel per lane, TH / 4 passes of four rows.
+// fused K1+K2, LDS-tiled form (the default): a workgroup rectifies + decodes 64 x 8 destination tiles, one pixel per lane,
+// two passes of four rows.
 //   0. (once per map, at slr_set_rectify_maps / slr_init_rectify_maps) tile_boxes_kernel reduces every tile's map
 //      entries to the bounding box of its source footprints with wave shuffles (a smooth map turns 64 x 8 into
 //      roughly 70 x 10 source pixels);
@@ -371,11 +369,11 @@ hipError_t launch_init_rectify_map(const double M[9], const double D[5], const d
 //      in the accumulator's high half-word for the consumer (SDWA operand select instead of a shift);
 //   3. the same per-pixel decode as K2.
 // The workgroups are persistent and software-pipelined (see below); an XCD-banded tile walk keeps horizontally
-// adjacent tiles on one L2.  PMC: 64 x 16 tiles fetch 1.01..1.07x the ideal bytes, 64 x 8 tiles 1.13..1.17x (their two
-// halo rows are re-read from HBM) but run 7 % faster (5 instead of 4 workgroups per CU).  A box that does not fit
+// adjacent tiles on one L2.  PMC: 64 x 8 tiles fetch 1.13..1.17x the ideal bytes (their two halo rows are re-read from
+// HBM), yet ran 7 % faster than the retired 64 x 16 tiles at 1.01..1.07x (5 instead of 4 workgroups per CU).  A box that does not fit
 // (wild maps) falls back, per tile, to the direct gather of the generic kernel.
 // ------------------------------------------------------------------------------------------------------
-constexpr int kTileW = 64, kTileH = 16;
+constexpr int kTileW = 64;
 
 // int4 per tile: x = x0 (multiple of 4), y = y0, z = BW4 (dwords per row), w = BH (rows); z == 0: no footprint
 __global__ __launch_bounds__(256) void tile_boxes_kernel(const int16_t *__restrict__ map_xy, int W, int H, int tiles_x,
@@ -423,7 +421,8 @@ __global__ __launch_bounds__(256) void tile_boxes_kernel(const int16_t *__restri
     }
 }
 
-// two tables in one buffer: 64x16 tiles (multi-frequency kernel: 14 planes) then 64x4 tiles (Gray kernel: 22..66 planes)
+// box tables in one buffer: 64x4 tiles (Gray kernel: 22..66 planes) then 64x8 tiles (multi-frequency kernel, and the Gray
+// kernel when its planes fit)
 constexpr int kGrayTileH = 4, kMidTileH = 8;
 static size_t tile_count(int W, int H, int tile_h)
 {
@@ -462,7 +461,7 @@ __device__ __host__ inline bool mid_box_fits(int BW4, int BH)
 }
 static size_t tiled_map_offset(int W, int H)
 {
-    const size_t b = (tile_count(W, H, kTileH) + tile_count(W, H, kGrayTileH) + tile_count(W, H, kMidTileH)) * sizeof(int4);
+    const size_t b = (tile_count(W, H, kGrayTileH) + tile_count(W, H, kMidTileH)) * sizeof(int4);
     return (b + 255) & ~(size_t)255;
 }
 // behind the two digests: two counters -- tiles with a footprint whose box does NOT fit the 64 x 8 form / the 128 x 8 form
@@ -538,18 +537,16 @@ hipError_t launch_tile_boxes(const int16_t *map_xy, const uint16_t *map_frac, in
     hipError_t me = hipMemsetAsync(nofit, 0, 16, s);
     if (me != hipSuccess) return me;
     const int tiles_x = (W + kTileW - 1) / kTileW;
-    SLR_LAUNCH(tile_boxes_kernel, dim3((unsigned)tile_count(W, H, kTileH)), dim3(256), 0, s, map_xy, W, H, tiles_x,
-                       kTileH, boxes);
+    int4 *const boxes8 = boxes + tile_count(W, H, kGrayTileH);
     SLR_LAUNCH(tile_boxes_kernel, dim3((unsigned)tile_count(W, H, kGrayTileH)), dim3(256), 0, s, map_xy, W, H, tiles_x,
-                       kGrayTileH, boxes + tile_count(W, H, kTileH));
+                       kGrayTileH, boxes);
     SLR_LAUNCH(tile_boxes_kernel, dim3((unsigned)tile_count(W, H, kMidTileH)), dim3(256), 0, s, map_xy, W, H, tiles_x,
-                       kMidTileH, boxes + tile_count(W, H, kTileH) + tile_count(W, H, kGrayTileH));
+                       kMidTileH, boxes8);
     unsigned *pk_t = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(boxes) + tiled_map_offset(W, H));
     SLR_LAUNCH(tile_maps_kernel, dim3((unsigned)tile_count(W, H, kMidTileH)), dim3(256), 0, s, map_xy, map_frac, W, H,
-                       tiles_x, boxes + tile_count(W, H, kTileH) + tile_count(W, H, kGrayTileH), pk_t, nofit);
+                       tiles_x, boxes8, pk_t, nofit);
     SLR_LAUNCH(tile_maps_wide_kernel, dim3((unsigned)wide_tile_count(W, H)), dim3(512), 0, s, map_xy, map_frac, W, H,
-                       (W + 2 * kTileW - 1) / (2 * kTileW), tiles_x, boxes + tile_count(W, H, kTileH) + tile_count(W, H, kGrayTileH),
-                       pk_t + tile_count(W, H, kMidTileH) * 512, nofit + 1);
+                       (W + 2 * kTileW - 1) / (2 * kTileW), tiles_x, boxes8, pk_t + tile_count(W, H, kMidTileH) * 512, nofit + 1);
     me = hipGetLastError();
     if (me != hipSuccess) return me;
     me = hipMemcpyAsync(nofit_host, nofit, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, s);   // the caller synchronises the stream
@@ -637,16 +634,16 @@ __device__ __forceinline__ int tile_sample(const uint8_t *tile, const TileTaps<N
 // Software pipeline (round 1 finding: with the frame NOT resident in the 256 MB Infinity Cache -- the real pipeline
 // alternates two 172 MB camera stacks -- the non-pipelined form was bound by HBM latency x the few workgroups that
 // happen to be in their fill phase: 129 us vs 100 us warm).  The workgroups are persistent; while a tile is being
-// decoded out of LDS, the global loads of the NEXT tile's box are already in flight into registers (2 rounds x 14
-// planes per thread) and are committed to LDS after the barrier that ends the current tile.  gfx9 has ONE in-order
-// counter for vector memory (vmcnt), so the loads a tile's decode itself needs (its 4x2 map entries) are issued
+// decoded out of LDS, the global loads of the NEXT tile's box are already in flight into registers (one dword of each
+// of the 14 planes per thread) and are committed to LDS after the barrier that ends the current tile.  gfx9 has ONE in-order
+// counter for vector memory (vmcnt), so the loads a tile's decode itself needs (its map entries) are issued
 // BEFORE the prefetch, and the prefetch is branch-free (out-of-box elements read a dummy address) so that the
-// compiler's s_waitcnt for the map entries is vmcnt(28) on every path and never drains the prefetch.
+// compiler's s_waitcnt for the map entries is vmcnt(14) on every path and never drains the prefetch.
 struct BoxGeom { int x0, y0, BW4, BH; bool any, fits; };
 
 // TWV == 2: the tile is 128 x TH, the union of two horizontally adjacent 64 x TH tiles of the box table (`tile` counts
 // 128-wide tiles, tiles_x of them per row; the table has tiles_x64 per row)
-template <int NP, int ROUNDS, int TWV, int NT>
+template <int NP, int TWV, int NT>
 __device__ __forceinline__ BoxGeom box_geom(const int4 *__restrict__ boxes, int tile, int budget, int tiles_x, int tiles_x64)
 {
     int4 box;
@@ -655,8 +652,8 @@ __device__ __forceinline__ BoxGeom box_geom(const int4 *__restrict__ boxes, int 
     BoxGeom g;
     g.x0 = box.x; g.y0 = box.y; g.BW4 = box.z; g.BH = box.w;
     g.any = g.BW4 > 0;
-    // the LDS budget, and the prefetch registers: at most ROUNDS x NT dwords per plane
-    g.fits = g.any && g.BW4 * g.BH <= NT * ROUNDS && g.BW4 * g.BH * (NP * 4) <= budget;
+    // the LDS budget, and the prefetch registers: at most NT dwords per plane
+    g.fits = g.any && g.BW4 * g.BH <= NT && g.BW4 * g.BH * (NP * 4) <= budget;
     return g;
 }
 
@@ -682,12 +679,12 @@ struct RectJobs { RectJob j[2]; };
 // NT == 512 (with TWV == 2): eight waves, waves 0-3 decode the left 64 columns of a 128 x 8 tile and waves 4-7 the right
 // ones out of ONE box that all 512 threads fetch in one round -- the source row segments are twice as long (fewer,
 // fuller cache lines per byte, see profiles/exp/boxread.hip) at the register cost of the 64 x 8 form.
-template <int TH, int ROUNDS, bool STRIDED, int TWV = 1, bool PACKED = false, int NT = 256>
-__global__ __launch_bounds__(NT, (NT == 512 ? 6 : ROUNDS == 1 && STRIDED ? 5 : 4)) void mf_rect_decode_lds_kernel(RectJobs jobs, int njobs, int pitch, int W, int H,
+template <bool STRIDED, int TWV = 1, bool PACKED = false, int NT = 256>
+__global__ __launch_bounds__(NT, (NT == 512 ? 6 : STRIDED ? 5 : 4)) void mf_rect_decode_lds_kernel(RectJobs jobs, int njobs, int pitch, int W, int H,
                                                                  int black_thr, const float *__restrict__ lut_g,
                                                                  int tiles_x, int tiles_y, int budget)
 {
-    constexpr int NP = SLR_MF_PLANES;
+    constexpr int NP = SLR_MF_PLANES, TH = kMidTileH;
     extern __shared__ __attribute__((aligned(16))) uint8_t tile[];
     __shared__ float lut[kLutWords + 1];
     load_lut(lut, lut_g);
@@ -711,7 +708,7 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 6 : ROUNDS == 1 && STRIDED ? 5 : 4
     uint8_t *__restrict__ valid = jobs.j[ji].valid;
     const unsigned *__restrict__ pk_t = jobs.j[ji].pk_t;
     constexpr bool packed = PACKED;                         // the launcher passes pk_t != null with PACKED only
-    static_assert(!PACKED || (TH == kMidTileH && ROUNDS == 1 && NT == 256 * TWV), "the pre-digested maps serve 64 x 8 / 128 x 8 tiles");
+    static_assert(!PACKED || NT == 256 * TWV, "the pre-digested maps serve 64 x 8 / 128 x 8 tiles");
     static_assert(NT == 256 || (NT == 512 && TWV == 2), "eight waves <=> 128-wide tiles");
     // Tile schedule.  Workgroup b runs on XCD b % 8 (round-robin dispatch); XCD x owns the band of `per` consecutive
     // tiles (row-major) [x*per, (x+1)*per), and its nbx workgroups walk the band together: in step i they decode the
@@ -721,50 +718,44 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 6 : ROUNDS == 1 && STRIDED ? 5 : 4
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const unsigned lane31 = (unsigned)lane & 31u;
 
-    // element e of a box (row-major dwords) that thread `tid` owns in round r: e = tid + 256 r
-    unsigned pre[ROUNDS][NP];
+    // element e of a box (row-major dwords) that thread `tid` owns: e = tid
+    unsigned pre[NP];
     auto issue = [&](const BoxGeom &g, bool live) {
         const int E = live && g.fits ? g.BH * g.BW4 : 0;
         const float inv = __builtin_amdgcn_rcpf((float)(g.BW4 > 0 ? g.BW4 : 1));   // v_rcp_f32: 1 ulp, see the margin below
+        const int e = (int)threadIdx.x;
+        const int rr = (int)(((float)e + 0.5f) * inv);      // e / BW4 (exact: e < 2^20, remainder margin 0.5/BW4)
+        const int cc = e - rr * g.BW4;
+        const int gx = g.x0 + 4 * cc, gy = g.y0 + rr;
+        // W % 4 == 0 and gx % 4 == 0: a dword is completely inside or completely outside the image
+        const bool in = e < E && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
+        // branch-free 32-bit offset: keeps the loads in the scalar-base + 32-bit-VGPR-offset addressing form
+        if constexpr (STRIDED) {
+            const unsigned off = in ? __umul24((unsigned)gy, (unsigned)pitch) + (unsigned)gx : 0xFFFFFFF0u;   // out of range -> 0
 #pragma unroll
-        for (int r = 0; r < ROUNDS; r++) {
-            const int e = (int)threadIdx.x + NT * r;
-            const int rr = (int)(((float)e + 0.5f) * inv);  // e / BW4 (exact: e < 2^20, remainder margin 0.5/BW4)
-            const int cc = e - rr * g.BW4;
-            const int gx = g.x0 + 4 * cc, gy = g.y0 + rr;
-            // W % 4 == 0 and gx % 4 == 0: a dword is completely inside or completely outside the image
-            const bool in = e < E && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-            // branch-free 32-bit offset: keeps the loads in the scalar-base + 32-bit-VGPR-offset addressing form
-            if constexpr (STRIDED) {
-                const unsigned off = in ? __umul24((unsigned)gy, (unsigned)pitch) + (unsigned)gx : 0xFFFFFFF0u;   // out of range -> 0
+            for (int p = 0; p < NP; p++)
+                pre[p] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)off, (int)(p * pstride), 0);
+        } else {
+            const unsigned off = (__umul24((unsigned)gy, (unsigned)pitch) + (unsigned)gx) & (0u - (unsigned)in);
 #pragma unroll
-                for (int p = 0; p < NP; p++)
-                    pre[r][p] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)off, (int)(p * pstride), 0);
-            } else {
-                const unsigned off = (__umul24((unsigned)gy, (unsigned)pitch) + (unsigned)gx) & (0u - (unsigned)in);
-#pragma unroll
-                for (int p = 0; p < NP; p++) pre[r][p] = *reinterpret_cast<const unsigned *>(plane(p) + off);
-            }
+            for (int p = 0; p < NP; p++) pre[p] = *reinterpret_cast<const unsigned *>(plane(p) + off);
         }
     };
     auto commit = [&](const BoxGeom &g) {                   // same predicate as issue(); outside the image -> 0
         const int E = g.BH * g.BW4;
         const float inv = __builtin_amdgcn_rcpf((float)g.BW4);
+        const int e = (int)threadIdx.x;
+        if (e < E) {
+            const int rr = (int)(((float)e + 0.5f) * inv);
+            const int cc = e - rr * g.BW4;
+            const int gx = g.x0 + 4 * cc, gy = g.y0 + rr;
+            const bool in = STRIDED || ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W);   // STRIDED: zeros came from the load
+            u32x2 *dst = reinterpret_cast<u32x2 *>(tile + (size_t)e * (NP * 4));
 #pragma unroll
-        for (int r = 0; r < ROUNDS; r++) {
-            const int e = (int)threadIdx.x + NT * r;
-            if (e < E) {
-                const int rr = (int)(((float)e + 0.5f) * inv);
-                const int cc = e - rr * g.BW4;
-                const int gx = g.x0 + 4 * cc, gy = g.y0 + rr;
-                const bool in = STRIDED || ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W);   // STRIDED: zeros came from the load
-                u32x2 *dst = reinterpret_cast<u32x2 *>(tile + (size_t)e * (NP * 4));
-#pragma unroll
-                for (int p = 0; p < NP; p += 2) {
-                    u32x2 w2;
-                    w2.x = in ? pre[r][p] : 0u; w2.y = in ? pre[r][p + 1] : 0u;
-                    dst[p >> 1] = w2;
-                }
+            for (int p = 0; p < NP; p += 2) {
+                u32x2 w2;
+                w2.x = in ? pre[p] : 0u; w2.y = in ? pre[p + 1] : 0u;
+                dst[p >> 1] = w2;
             }
         }
     };
@@ -774,7 +765,7 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 6 : ROUNDS == 1 && STRIDED ? 5 : 4
     const int tiles_x64 = (W + kTileW - 1) / kTileW;
     constexpr int QH = TH / 4, NPASS = NT == 512 ? QH : QH * TWV;   // passes per 64-wide half, passes of a wave per tile
     const int wrow = NT == 512 ? (wv & 3) : wv;             // the wave's row inside a pass
-    BoxGeom gc = box_geom<NP, ROUNDS, TWV, NT>(boxes, cur, budget, tiles_x, tiles_x64);
+    BoxGeom gc = box_geom<NP, TWV, NT>(boxes, cur, budget, tiles_x, tiles_x64);
     issue(gc, true);
     for (int it = 1;; it++) {
         if (gc.fits) commit(gc);
@@ -782,7 +773,7 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 6 : ROUNDS == 1 && STRIDED ? 5 : 4
         const int nl = lb + it * nbx;
         const bool has_next = nl < per && xcd * per + nl < T;
         const int nxt = has_next ? xcd * per + nl : cur;
-        const BoxGeom gn = box_geom<NP, ROUNDS, TWV, NT>(boxes, nxt, budget, tiles_x, tiles_x64);
+        const BoxGeom gn = box_geom<NP, TWV, NT>(boxes, nxt, budget, tiles_x, tiles_x64);
 
         const int ty = cur / tiles_x, tx = cur - ty * tiles_x;
         // map entries of all passes first (see the header: they must be older than the prefetch)
@@ -855,217 +846,6 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 6 : ROUNDS == 1 && STRIDED ? 5 : 4
     }
 }
 
-#ifdef SLR_ALL_FORMS
-// ------------------------------------------------------------------------------------------------------
-// fused K1+K2, sliding-window form (SLR_OPT_RECT_DECODE_ALGO = 3): the pipelined kernel above re-reads the two halo
-// rows of every 64 x 8 tile from HBM (1.13..1.17x the ideal traffic).  Here a workgroup walks DOWN a tile column and
-// keeps the source rows in a 16-row LDS ring (slot = source row & 15): the next tile only loads the rows below the
-// ones already there.  Work item = (tile column, vertical segment of the XCD's band of tile rows); the items of one
-// segment are handed to consecutive workgroups, so horizontally adjacent tiles are decoded at the same time and share
-// their source lines in L2.  All tiles of an item use one LDS geometry (the union of their source column ranges).
-// ------------------------------------------------------------------------------------------------------
-constexpr int kRingRows = 16, kRingBW = 20;               // ring: 16 source rows x <= 20 dwords x 14 planes = 17.9 KB
-
-struct RingTile {                                        // one 64 x 8 tile and the LDS geometry of its item
-    int tx, ty, item;
-    int x0, bw;                                          // item geometry: source columns [x0, x0 + 4 bw)
-    int y0, bh;                                          // this tile's source rows [y0, y0 + bh)
-    bool any, ok, valid;                                 // has a footprint / the item fits the ring / tile exists
-};
-
-__global__ __launch_bounds__(256, 5) void mf_rect_decode_ring_kernel(RectJobs jobs, int njobs, int pitch, int W, int H,
-                                                                     int black_thr, const float *__restrict__ lut_g,
-                                                                     int tiles_x, int tiles_y, int seg_len)
-{
-    constexpr int NP = SLR_MF_PLANES, TH = kMidTileH;
-    extern __shared__ __attribute__((aligned(16))) uint8_t tile[];
-    __shared__ float lut[kLutWords + 1];
-    load_lut(lut, lut_g);
-    const unsigned nblk = gridDim.x / (unsigned)njobs;
-    const bool second = blockIdx.x >= nblk;
-    const unsigned bid = second ? blockIdx.x - nblk : blockIdx.x;
-    const int ji = second ? 1 : 0;
-    auto plane = [&](int p) -> const uint8_t * { return jobs.j[ji].pl.p[p]; };
-    const int16_t *__restrict__ map_xy = jobs.j[ji].map_xy;
-    const uint16_t *__restrict__ map_frac = jobs.j[ji].map_frac;
-    const int4 *__restrict__ boxes = jobs.j[ji].boxes;
-    float *__restrict__ phase = jobs.j[ji].phase;
-    uint8_t *__restrict__ valid = jobs.j[ji].valid;
-    const int xcd = (int)(bid & 7u), lb = (int)(bid >> 3), nbx = (int)(nblk >> 3);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned lane31 = (unsigned)lane & 31u;
-
-    // schedule: XCD x owns tile rows [band0, band1); items = columns x segments of seg_len tile rows, segment-major
-    const int R = (tiles_y + 7) >> 3;
-    const int band0 = xcd * R, band1 = band0 + R < tiles_y ? band0 + R : tiles_y;
-    const int nseg = band1 > band0 ? (band1 - band0 + seg_len - 1) / seg_len : 0;
-    const int nitems = nseg * tiles_x;
-
-    auto enter_item = [&](int item, RingTile &t) {         // geometry of an item = union over its tiles
-        t.item = item;
-        t.valid = item < nitems;
-        if (!t.valid) return;
-        const int seg = item / tiles_x;
-        t.tx = item - seg * tiles_x;
-        const int r0 = band0 + seg * seg_len, r1 = r0 + seg_len < band1 ? r0 + seg_len : band1;
-        int xa = 0x7FFFFFFF, xb = -0x7FFFFFFF, mh = 0;
-        for (int r = r0; r < r1; r++) {
-            const int4 b = boxes[r * tiles_x + t.tx];
-            if (b.z > 0) {
-                xa = b.x < xa ? b.x : xa;
-                xb = b.x + 4 * b.z > xb ? b.x + 4 * b.z : xb;
-                mh = b.w > mh ? b.w : mh;
-            }
-        }
-        t.x0 = xb > xa ? xa : 0;
-        t.bw = xb > xa ? (xb - xa) >> 2 : 1;
-        t.ok = t.bw <= kRingBW && mh <= kRingRows - 2 && t.bw * mh <= 256;
-        t.ty = r0;
-    };
-    auto load_box = [&](RingTile &t) {
-        const int4 b = boxes[t.ty * tiles_x + t.tx];
-        t.any = b.z > 0;
-        t.y0 = b.y; t.bh = b.w;
-    };
-    auto advance = [&](const RingTile &c, RingTile &n) {   // the tile after c in this workgroup's walk
-        n = c;
-        const int seg = c.item / tiles_x;
-        const int r1 = band0 + (seg + 1) * seg_len < band1 ? band0 + (seg + 1) * seg_len : band1;
-        if (c.ty + 1 < r1) n.ty = c.ty + 1;
-        else enter_item(c.item + nbx, n);
-        if (n.valid) load_box(n);
-    };
-
-    // ring state (uniform): rows [lo, hi) of geometry (rx0, rbw) are in LDS
-    int lo = 0, hi = 0, rx0 = 0, rbw = -1;
-    struct Ld { int y0, y1, x0, bw; bool on; };
-    auto plan = [&](const RingTile &t, int plo, int phi, int px0, int pbw) -> Ld {   // rows to load for tile t
-        Ld l; l.on = t.valid && t.ok && t.any; l.x0 = t.x0; l.bw = t.bw; l.y0 = l.y1 = 0;
-        if (!l.on) return l;
-        const bool cont = pbw == t.bw && px0 == t.x0 && t.y0 >= plo && t.y0 <= phi;
-        l.y0 = cont ? (phi > t.y0 ? phi : t.y0) : t.y0;
-        l.y1 = t.y0 + t.bh;
-        if (l.y1 < l.y0) l.y1 = l.y0;
-        return l;
-    };
-    auto after = [&](const RingTile &t, const Ld &l, int &plo, int &phi, int &px0, int &pbw) {   // ring after the commit
-        if (!l.on) return;
-        const bool cont = pbw == t.bw && px0 == t.x0 && t.y0 >= plo && t.y0 <= phi;
-        phi = cont ? (phi > l.y1 ? phi : l.y1) : l.y1;
-        plo = t.y0; px0 = t.x0; pbw = t.bw;
-    };
-
-    unsigned pre[NP];
-    auto issue = [&](const Ld &l) {
-        const int E = l.on ? (l.y1 - l.y0) * l.bw : 0;
-        const float inv = __builtin_amdgcn_rcpf((float)(l.bw > 0 ? l.bw : 1));
-        const int e = (int)threadIdx.x;
-        const int rr = (int)(((float)e + 0.5f) * inv);
-        const int cc = e - rr * l.bw;
-        const int gx = l.x0 + 4 * cc, gy = l.y0 + rr;
-        const bool in = e < E && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-        const unsigned off = (__umul24((unsigned)gy, (unsigned)pitch) + (unsigned)gx) & (0u - (unsigned)in);
-#pragma unroll
-        for (int p = 0; p < NP; p++) pre[p] = *reinterpret_cast<const unsigned *>(plane(p) + off);
-    };
-    auto commit = [&](const Ld &l) {
-        if (!l.on) return;
-        const int E = (l.y1 - l.y0) * l.bw;
-        const int e = (int)threadIdx.x;
-        if (e < E) {
-            const float inv = __builtin_amdgcn_rcpf((float)l.bw);
-            const int rr = (int)(((float)e + 0.5f) * inv);
-            const int cc = e - rr * l.bw;
-            const int gx = l.x0 + 4 * cc, gy = l.y0 + rr;
-            const bool in = (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-            u32x2 *dst = reinterpret_cast<u32x2 *>(tile + (size_t)(((gy & (kRingRows - 1)) * l.bw + cc) * (NP * 4)));
-#pragma unroll
-            for (int p = 0; p < NP; p += 2) {
-                u32x2 w2;
-                w2.x = in ? pre[p] : 0u; w2.y = in ? pre[p + 1] : 0u;
-                dst[p >> 1] = w2;
-            }
-        }
-    };
-
-    RingTile cur;
-    enter_item(lb, cur);
-    if (!cur.valid) return;
-    load_box(cur);
-    Ld ld = plan(cur, lo, hi, rx0, rbw);
-    issue(ld);
-    for (;;) {
-        commit(ld);
-        after(cur, ld, lo, hi, rx0, rbw);
-        __syncthreads();
-        RingTile nxt;
-        advance(cur, nxt);
-        const int col = cur.tx * kTileW + lane;
-        unsigned xy[TH / 4], fr[TH / 4];
-#pragma unroll
-        for (int q = 0; q < TH / 4; q++) {                  // this tile's map entries first (older than the prefetch)
-            const int row = cur.ty * TH + 4 * q + wv;
-            const bool inb = row < H && col < W;
-            const unsigned m = inb ? (unsigned)row * (unsigned)W + (unsigned)col : 0u;
-            xy[q] = *reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(map_xy) + m * 4u);
-            fr[q] = *reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(map_frac) + m * 2u);
-        }
-        const Ld ldn = plan(nxt, lo, hi, rx0, rbw);
-        issue(ldn);
-#pragma unroll
-        for (int q = 0; q < TH / 4; q++) {
-            const int row = cur.ty * TH + 4 * q + wv;
-            const bool inb = row < H && col < W;
-            const unsigned m = (unsigned)row * (unsigned)W + (unsigned)col;
-            int v;
-            float ph;
-            if (cur.ok) {
-                // tile_taps_map with ring addressing: row slot = source row & 15, columns relative to the item
-                TileTaps<NP> k;
-                const int sx = (int)(short)(xy[q] & 0xFFFFu), sy = (int)xy[q] >> 16;
-                const bool out = !inb || !cur.any || (unsigned)(sx + 1) > (unsigned)W || (unsigned)(sy + 1) > (unsigned)H;
-                const unsigned fx = fr[q] & 31u, fy = (fr[q] >> 5) & 31u;
-                const unsigned wxp = out ? 0u : __umul24(fx, 0xFFFFu) + 32u;
-                unsigned w0 = __umul24(wxp, (32u - fy) << 6);
-                const unsigned w1 = __umul24(wxp, fy << 6);
-                w0 = w0 == 0x10000u ? 0xFFFFu : w0;
-                const int bx = out ? 0 : sx - cur.x0;
-                const int s0 = out ? 0 : (sy & (kRingRows - 1)), s1 = out ? 0 : ((sy + 1) & (kRingRows - 1));
-                k.a0 = __mul24(__mul24(s0, cur.bw) + (bx >> 2), NP * 4);
-                k.a1 = __mul24(__mul24(s1, cur.bw) + (bx >> 2), NP * 4);
-                k.sel = __umul24((unsigned)bx & 3u, 0x10001u) + 0x0C010C00u;
-                k.w0 = __builtin_bit_cast(u16x2, w0);
-                k.w1 = __builtin_bit_cast(u16x2, w1);
-                int acc[NP];
-#pragma unroll
-                for (int p = 0; p < NP; p++) acc[p] = tile_sample<NP, 6>(tile, k, p);
-                ph = mf_pixel_sh<16>(acc, black_thr, lut, v);
-            } else {                                        // the item does not fit the ring: direct gather
-                Tap t = make_tap((int)(short)(xy[q] & 0xFFFFu), (int)xy[q] >> 16, fr[q], pitch, W, H);
-                if (!inb) t.kind = 1;
-                int gpx[NP];
-#pragma unroll 1
-                for (int p = 0; p < NP; p++) gpx[p] = cur.any ? sample(plane(p), pitch, W, H, t) : 0;
-                ph = mf_pixel(gpx, black_thr, lut, v);
-            }
-            if (valid) {
-                const unsigned long long bal = __ballot(v != 0);
-                const unsigned half = (lane & 32) ? (unsigned)(bal >> 32) : (unsigned)bal;
-                const unsigned vw = __umul24((half >> lane31) & 0xFu, 0x204081u) & 0x01010101u;
-                if (inb && (lane & 3) == 0) __builtin_nontemporal_store(vw, reinterpret_cast<unsigned *>(valid + m));
-            } else {
-                ph = v ? ph : kInvalidPhase;                // folded flag (see launch_mf_decode)
-            }
-            if (inb) __builtin_nontemporal_store(ph, reinterpret_cast<float *>(reinterpret_cast<char *>(phase) + m * 4u));
-        }
-        if (!nxt.valid) break;
-        __syncthreads();
-        cur = nxt;
-        ld = ldn;
-    }
-}
-#endif  // SLR_ALL_FORMS
-
 static unsigned pick_blocks(size_t groups)
 {
     // One workgroup per 256 work items (no persistent grid-stride): with a capped grid the last sweep leaves
@@ -1107,62 +887,22 @@ static bool rect_lds_ok(const MfPlanes &pl, int pitch, int W, int H, const float
 static hipError_t launch_rect_lds(const RectJob *jobs, int njobs, int pitch, int W, int H, int black_thr,
                                   const float *atan_lut, int rect_algo, hipStream_t s)
 {
-    int tiles_x = (W + kTileW - 1) / kTileW;
-    // (forms 2, 3 and 4 are measured-dominated -- DESIGN section 9 -- and compiled with -DSLR_ALL_FORMS only; without it
-    // slr_set_option refuses them)
-#ifdef SLR_ALL_FORMS
-    if (rect_algo == 3) {                                // sliding-window form
-        const int tiles_y8 = (H + kMidTileH - 1) / kMidTileH;
-        RectJobs jr;
-        jr.j[0] = jobs[0]; jr.j[1] = jobs[njobs - 1];
-        const size_t off8 = tile_count(W, H, kTileH) + tile_count(W, H, kGrayTileH);
-        jr.j[0].boxes += off8; jr.j[1].boxes += off8;
-        const size_t lds = (size_t)kRingRows * kRingBW * SLR_MF_PLANES * 4 + 16;
-        static DevSlots ring_cache;
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        int ring_res = ring_cache.get(dev);
-        if (!ring_res) {
-            int per_cu = 0, cus = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mf_rect_decode_ring_kernel, 256, lds) != hipSuccess || per_cu < 1) per_cu = 4;
-            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-            ring_res = per_cu * cus;
-            ring_cache.put(dev, ring_res);
-        }
-        const int res = (tl_debug.rect_resident > 0 ? tl_debug.rect_resident : ring_res) / njobs;
-        int nbx = res / 8 > 0 ? res / 8 : 1;
-        const int R = (tiles_y8 + 7) / 8;                    // tile rows per XCD band
-        if (nbx > R * tiles_x) nbx = R * tiles_x;
-        int seg_len = (R * tiles_x + 4 * nbx - 1) / (4 * nbx);   // ~4 items per workgroup
-        if (seg_len < 4) seg_len = 4;
-        if (seg_len > R) seg_len = R > 0 ? R : 1;
-        SLR_LAUNCH(mf_rect_decode_ring_kernel, dim3(8u * (unsigned)nbx * (unsigned)njobs), dim3(256), lds, s, jr, njobs,
-                           pitch, W, H, black_thr, atan_lut, tiles_x, tiles_y8, seg_len);
-        return hipGetLastError();
-    }
-    const bool mid = rect_algo != 2;                     // default: 64 x 8 tiles, one prefetch round; 2: 64 x 16, two
-    const bool wide8 = rect_algo == 5;                   // 5: 128 x 8 tiles, 512 threads, one round, pre-digested map
-    const bool wide = rect_algo == 4 || wide8;           // 4: 128 x 8 tiles (pairs of 64 x 8 table entries), two rounds
-#else
-    constexpr bool mid = true;                           // 6 (and whatever else arrives here): 64 x 8 tiles, one prefetch round
-    const bool wide8 = rect_algo == 5;                   // 5: 128 x 8 tiles, 512 threads, one round, pre-digested map
-    const bool wide = wide8;
-#endif
+    // 6 (and whatever else arrives here): 64 x 8 tiles; 5: 128 x 8 tiles (pairs of 64 x 8 table entries), 512 threads, its own
+    // pre-digested map
+    const bool wide8 = rect_algo == 5;
     // persistent workgroups: as many as are resident at once (a multiple of 8 per job for the XCD bands), never more
     // than one per tile
-    const int th = mid ? kMidTileH : kTileH;
-    const int tiles_yy = (H + th - 1) / th;
-    if (wide) tiles_x = (W + 2 * kTileW - 1) / (2 * kTileW);
-    const int budget = wide8 ? kWideBudget : wide ? 27 * 1024 : mid ? kMidBudget : 24 * 1024;   // 14 planes x ~(tile width + 8) x (th + 7) source bytes
-    const size_t box_off = mid ? tile_count(W, H, kTileH) + tile_count(W, H, kGrayTileH) : 0;
+    const int tiles_x = wide8 ? (W + 2 * kTileW - 1) / (2 * kTileW) : (W + kTileW - 1) / kTileW;
+    const int tiles_yy = (H + kMidTileH - 1) / kMidTileH;
+    const int budget = wide8 ? kWideBudget : kMidBudget;   // 14 planes x ~(tile width + 8) x 15 source bytes
     RectJobs j;
     j.j[0] = jobs[0]; j.j[1] = jobs[njobs - 1];
     for (int jq = 0; jq < 2; jq++) {                      // the tiled map copy lives behind the box tables (launch_tile_boxes)
         const char *basep = reinterpret_cast<const char *>(j.j[jq].boxes);
-        j.j[jq].pk_t = mid && !wide && !tl_debug.no_tiled_map ? reinterpret_cast<const unsigned *>(basep + tiled_map_offset(W, H)) : nullptr;
-        if (wide8) j.j[jq].pk_t = reinterpret_cast<const unsigned *>(basep + tiled_map_offset(W, H)) + tile_count(W, H, kMidTileH) * 512;
+        const unsigned *pk8 = reinterpret_cast<const unsigned *>(basep + tiled_map_offset(W, H));
+        j.j[jq].pk_t = wide8 ? pk8 + tile_count(W, H, kMidTileH) * 512 : tl_debug.no_tiled_map ? nullptr : pk8;
+        j.j[jq].boxes += tile_count(W, H, kGrayTileH);    // the 64 x 8 table
     }
-    j.j[0].boxes += box_off; j.j[1].boxes += box_off;
     // resident workgroups of this kernel on the CURRENT device (cached per device and kernel variant)
     // strided planes?  (both jobs)
     bool strided = true;
@@ -1175,25 +915,19 @@ static hipError_t launch_rect_lds(const RectJob *jobs, int njobs, int pitch, int
         strided = strided && ok;
     }
     if (tl_debug.no_buffer_form) strided = false;         // tests: force the pointer form
-    static DevSlots resident_cache[4][2];
+    static DevSlots resident_cache[2][2];
     int dev = 0;
     (void)hipGetDevice(&dev);
-    DevSlots &resident_of = resident_cache[wide8 ? 3 : wide ? 2 : mid][strided];
+    DevSlots &resident_of = resident_cache[wide8][strided];
     int resident_slot = resident_of.get(dev);
     if (!resident_slot) {
         int per_cu = 0, cus = 0;
         const size_t dyn = (size_t)budget + 16;
         const hipError_t e =
-            wide8 ? (strided ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mf_rect_decode_lds_kernel<kMidTileH, 1, true, 2, true, 512>, 512, dyn)
-                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mf_rect_decode_lds_kernel<kMidTileH, 1, false, 2, true, 512>, 512, dyn)) :
-#ifdef SLR_ALL_FORMS
-            wide ? (strided ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mf_rect_decode_lds_kernel<kMidTileH, 2, true, 2>, 256, dyn)
-                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mf_rect_decode_lds_kernel<kMidTileH, 2, false, 2>, 256, dyn)) :
-            !mid ? (strided ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mf_rect_decode_lds_kernel<kTileH, 2, true>, 256, dyn)
-                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mf_rect_decode_lds_kernel<kTileH, 2, false>, 256, dyn)) :
-#endif
-                  (strided ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mf_rect_decode_lds_kernel<kMidTileH, 1, true, 1, true>, 256, dyn)
-                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mf_rect_decode_lds_kernel<kMidTileH, 1, false, 1, true>, 256, dyn));
+            wide8 ? (strided ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mf_rect_decode_lds_kernel<true, 2, true, 512>, 512, dyn)
+                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mf_rect_decode_lds_kernel<false, 2, true, 512>, 512, dyn))
+                  : (strided ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mf_rect_decode_lds_kernel<true, 1, true>, 256, dyn)
+                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mf_rect_decode_lds_kernel<false, 1, true>, 256, dyn));
         if (e != hipSuccess || per_cu < 1) per_cu = 4;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
         resident_slot = per_cu * cus;
@@ -1205,31 +939,12 @@ static hipError_t launch_rect_lds(const RectJob *jobs, int njobs, int pitch, int
     int nbx = res / 8 < per ? res / 8 : per;
     if (nbx < 1) nbx = 1;
     const dim3 grid(8u * (unsigned)nbx * (unsigned)njobs);
-#define SLR_RECT_LAUNCH(TH_, R_, S_)                                                                                  \
-    SLR_LAUNCH((mf_rect_decode_lds_kernel<TH_, R_, S_>), grid, dim3(256), (size_t)budget + 16, s, j, njobs, pitch, W, \
-                       H, black_thr, atan_lut, tiles_x, tiles_yy, budget)
-    if (wide8) {
-        if (strided) SLR_LAUNCH((mf_rect_decode_lds_kernel<kMidTileH, 1, true, 2, true, 512>), grid, dim3(512), (size_t)budget + 16, s, j, njobs,
-                                        pitch, W, H, black_thr, atan_lut, tiles_x, tiles_yy, budget);
-        else         SLR_LAUNCH((mf_rect_decode_lds_kernel<kMidTileH, 1, false, 2, true, 512>), grid, dim3(512), (size_t)budget + 16, s, j, njobs,
-                                        pitch, W, H, black_thr, atan_lut, tiles_x, tiles_yy, budget);
-    }
-#ifdef SLR_ALL_FORMS
-    else if (wide) {
-        if (strided) SLR_LAUNCH((mf_rect_decode_lds_kernel<kMidTileH, 2, true, 2>), grid, dim3(256), (size_t)budget + 16, s, j, njobs,
-                                        pitch, W, H, black_thr, atan_lut, tiles_x, tiles_yy, budget);
-        else         SLR_LAUNCH((mf_rect_decode_lds_kernel<kMidTileH, 2, false, 2>), grid, dim3(256), (size_t)budget + 16, s, j, njobs,
-                                        pitch, W, H, black_thr, atan_lut, tiles_x, tiles_yy, budget);
-    }
-    else if (!mid) { if (strided) SLR_RECT_LAUNCH(kTileH, 2, true); else SLR_RECT_LAUNCH(kTileH, 2, false); }
-#endif
-    else if (mid && j.j[0].pk_t) {
-        if (strided) SLR_LAUNCH((mf_rect_decode_lds_kernel<kMidTileH, 1, true, 1, true>), grid, dim3(256), (size_t)budget + 16, s, j, njobs,
-                                        pitch, W, H, black_thr, atan_lut, tiles_x, tiles_yy, budget);
-        else         SLR_LAUNCH((mf_rect_decode_lds_kernel<kMidTileH, 1, false, 1, true>), grid, dim3(256), (size_t)budget + 16, s, j, njobs,
-                                        pitch, W, H, black_thr, atan_lut, tiles_x, tiles_yy, budget);
-    }
-    else { if (strided) SLR_RECT_LAUNCH(kMidTileH, 1, true); else SLR_RECT_LAUNCH(kMidTileH, 1, false); }
+#define SLR_RECT_LAUNCH(NT_, ...)                                                                                     \
+    SLR_LAUNCH((mf_rect_decode_lds_kernel<__VA_ARGS__>), grid, dim3(NT_), (size_t)budget + 16, s, j, njobs, pitch, W, H, \
+               black_thr, atan_lut, tiles_x, tiles_yy, budget)
+    if (wide8) { if (strided) SLR_RECT_LAUNCH(512, true, 2, true, 512); else SLR_RECT_LAUNCH(512, false, 2, true, 512); }
+    else if (j.j[0].pk_t) { if (strided) SLR_RECT_LAUNCH(256, true, 1, true); else SLR_RECT_LAUNCH(256, false, 1, true); }
+    else { if (strided) SLR_RECT_LAUNCH(256, true); else SLR_RECT_LAUNCH(256, false); }
 #undef SLR_RECT_LAUNCH
     return hipGetLastError();
 }
@@ -1591,14 +1306,14 @@ hipError_t launch_gray_decode(const GrayPlanes &pl, int n_col_bits, int n_row_bi
         const int tiles_x = (W + kTileW - 1) / kTileW;
         // 64 x 8 tiles when a typical box (72 source bytes x 11 rows) of all planes fits 32 KB, else 64 x 4; the LDS
         // request is sized for a generous box of this plane count (boxes beyond it take the per-tile gather fallback)
-        const bool mid = (size_t)nplanes * 72 * 11 <= 32 * 1024 && rect_algo != 2 && !tl_debug.gray_small_tiles;
+        const bool mid = (size_t)nplanes * 72 * 11 <= 32 * 1024 && !tl_debug.gray_small_tiles;
         const int th = mid ? kMidTileH : kGrayTileH;
         size_t want = (size_t)nplanes * 76 * (mid ? 12 : 7);
         want = want < 8 * 1024 ? 8 * 1024 : (want > 32 * 1024 ? 32 * 1024 : want);
         const int budget = (int)((want + 255) & ~(size_t)255);
         const int tiles_y = (H + th - 1) / th;
         const unsigned blocks = ((unsigned)(tiles_x * tiles_y) + 7u) & ~7u;
-        const int4 *boxes = (const int4 *)tile_boxes + tile_count(W, H, kTileH) + (mid ? tile_count(W, H, kGrayTileH) : 0);
+        const int4 *boxes = (const int4 *)tile_boxes + (mid ? tile_count(W, H, kGrayTileH) : 0);
         long long st = nplanes > 1 ? (long long)(pl.p[1] - pl.p[0]) : 0;
         bool strided = st >= (long long)H * pitch && st * nplanes < (1ll << 31) && !tl_debug.no_buffer_form;
         for (int i = 2; i < nplanes && strided; i++) strided = (long long)(pl.p[i] - pl.p[0]) == st * i;

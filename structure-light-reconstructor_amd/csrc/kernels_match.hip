@@ -3,7 +3,7 @@
 //
 // Both search along one rectified image row, so a row of the right camera lives in LDS and rows are the
 // unit of parallelism (one workgroup per row).  Neither is HBM-bound (PMC: VALU issue + LDS): K4 is an exact
-// indexed first-match search (LDS radix sort + bin index), K5 an LDS sort + wave-parallel speculative walk that
+// indexed first-match search (LDS hash + counting-sort bin index), K5 an LDS sort + wave-parallel speculative walk that
 // reproduces the reference's sequential `kstart` dependency exactly (wavefront shuffles do the prefix-max).
 //
 // Reference behaviour restated (never copied):
@@ -18,7 +18,7 @@
 
 // stage ablation of the match kernels (profiles/k4_stages.sh): "leave after stage N, outputs are not written".  Only builds with
 // -DSLR_DEBUG_HOOKS contain the exits; the production kernels carry none of them.  SLR_K4_ABL (timing only, wrong results): bit 0 no
-// output stores, 1 no table gathers, 2 no slow-path quotients (512 x 8 shapes), 3 the phases of 64 rows from the middle of the frame,
+// output stores, 1 no table gathers, 2 unused (it served the retired 512 x 8 shapes), 3 the phases of 64 rows from the middle of the frame,
 // hot in L2 (round 5: what a fused decode -> match launch could save on the match side -- nothing, profiles/exp/r05/fusion_bounds.txt).
 #if !defined(SLR_EXPERIMENTS) && (defined(SLR_K4_ABL) || defined(SLR_DEBUG_HOOKS))
 #error "SLR_K4_ABL / SLR_DEBUG_HOOKS are experiment switches: build with -DSLR_EXPERIMENTS"
@@ -164,29 +164,13 @@ __global__ __launch_bounds__(256) void mf_match_kernel(const float *__restrict__
 // ------------------------------------------------------------------------------------------------------
 // K4 (exact indexed form).  The sweep above is O(W) per left pixel; the same answer is available in
 // O(1) expected because "first k (ascending) with |phiL - phiR[k]| < 0.1" only ever selects, for each DISTINCT
-// right phase value, that value's smallest column.  One 1024-thread workgroup per row (4 pixels per thread, all
-// row I/O vectorised and issued up front):
-//   1. the right row's keys (12-bit phase bin, 4-bit hash of the value, column) are radix-sorted in LDS on the 16
-//      group bits only (2 passes, stable -> ascending column inside a group).  Any function of phi is a valid group
-//      key: equal phases share it, and colliding distinct values merely yield a few extra run heads;
-//   2. run heads (phase differs from its predecessor) are compacted -> (phi, min column) pairs grouped by bin;
-//   3. a suffix-min scan builds binfirst[b] = first pair whose bin >= b; two values closer than 0.1001 are at most
-//      one 0.25-wide bin apart, so bins [b-1, b+1] of phiL are a superset of its candidates;
-//   4. every left pixel applies the reference's own f32 predicate fabsf(phiL - phiR) < 0.1f to that window
-//      (~6 pairs, four per LDS round trip) and keeps the smallest column -- identical to the linear sweep (asserted
-//      against the oracle AND the sweep kernel on adversarial rows and on the whole 4096x3000 frame);
-//   5. Utilities::undistortPoints comes from per-pixel tables, Q*p and the three divisions stay f64.
-// Phase split at 4096x3000 (profiles/k4_stages.sh): loads 21 us, sort 66, heads 13, bins 10, queries 43, f64 + stores 55.
+// right phase value, that value's smallest column.  The (phi, smallest column) pairs of a row are grouped by 0.25-wide
+// phase bin; two values closer than 0.1001 are at most one bin apart, so bins [b-1, b+1] of phiL are a superset of its
+// candidates, and every left pixel applies the reference's own f32 predicate fabsf(phiL - phiR) < 0.1f to that window
+// and keeps the smallest column -- identical to the linear sweep (asserted against the oracle AND the sweep kernel on
+// adversarial rows and on the whole 4096x3000 frame).  Utilities::undistortPoints comes from per-pixel tables, Q*p and
+// the three divisions stay f64.
 // ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned sortable_key(float f)
-{
-    const unsigned b = __float_as_uint(f);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float key_to_float(unsigned k)
-{
-    return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-}
 
 constexpr int kBins = 4096;                              // 0.25-wide bins over [-512, 512), clamped outside
 __device__ __forceinline__ int phase_bin(float p)
@@ -316,8 +300,8 @@ __device__ __forceinline__ void k4_emit(const int best[IPT], size_t base, int k0
 }
 
 // ------------------------------------------------------------------------------------------------------
-// K4 (exact indexed form, hash + counting-sort build).  Same candidate-window query as the sorted form below, but
-// the per-bin lists of DISTINCT right phases are built without a sort:
+// K4 (exact indexed form, hash + counting-sort build).  The per-bin lists of DISTINCT right phases are built without a
+// sort:
 //   A. the reference's phases are heavily quantised (atan of an INTEGER quotient, Q1): a 4096-pixel row holds only a
 //      few hundred distinct values.  An LDS open-addressing hash table keyed by the phase bits keeps, per distinct
 //      value, its smallest column (atomicCAS claims the slot, atomicMin on the column) -- "first k ascending" can only
@@ -479,14 +463,7 @@ struct K4Lean {
 // evaluates differently -- the predicate sees the EXACT difference of the two phases (f64: the difference of two floats of this
 // range is exact in 53 bits) and the disparity reaches the double unrounded.  The index is the same: its bins only have to
 // hold every pair closer than 0.1 + rounding, which a 0.25-wide bin and its neighbours do under either predicate.
-// NOHASH (round 6): the index WITHOUT the hash dedup.  The dedup never changes a result -- the query takes the smallest matching column
-// whatever else is in its window -- it only bounds the bins of rows with many equal phases.  So every valid right pixel (minus an
-// in-thread left neighbour of the same value) goes straight into the counting sort: no 64 KB table to clear, no CAS / atomicMin probes
-// (the random-slot LDS traffic behind the kernel's bank conflicts), two barriers fewer per row.  A row in which some bin ends up with
-// more than kHeavyBin entries (flat or saturated regions) is rebuilt with the hash dedup in the same workgroup: bit-equal either way.
-// MEASURED SLOWER on the reference's own phases (see the launch site): SLR_OPT_MF_MATCH_ALGO = 9 in FORMS=all builds only.
-constexpr unsigned kHeavyBin = 32;
-template <int BLOCK, bool HAS_T, bool XCHG = false, bool TAME = false, bool X87 = false, bool NOHASH = false>
+template <int BLOCK, bool HAS_T, bool XCHG = false, bool TAME = false, bool X87 = false>
 __global__ __launch_bounds__(BLOCK, (BLOCK == 1024 ? 8 : 4)) void mf_match_lean_kernel(const float *__restrict__ phaseL, const uint8_t *__restrict__ validL,
                                                               const float *__restrict__ phaseR, const uint8_t *__restrict__ validR,
                                                               int W, int H, int row0, K4Lean kc, int stop,
@@ -558,39 +535,37 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == 1024 ? 8 : 4)) void mf_match_lean_
         const bool dup = i > 0 && ok && vr[i - 1] && bits[i] == bits[i - 1];
         cand[i] = ok && !dup;
         slot[i] = (bits[i] * 2654435761u) >> (32 - __builtin_ctz(TS));
-        if (NOHASH && cand[i]) repmask |= 1u << i;       // without the dedup every candidate is a representative
     }
-    // A. (hash form, or a heavy row of the NOHASH form) distinct values and their smallest column, as mf_match_binned_kernel; the four
-    //    first probes are independent LDS atomics in flight together, a collision continues in the loop.  Leaves repmask and the
-    //    zeroed bin counters behind a barrier.
-    auto hash_dedup = [&]() {
-        {
-            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-            const u32x4 e4 = {kEmpty, kEmpty, kEmpty, kEmpty};
-            u32x4 *const t4 = reinterpret_cast<u32x4 *>(sh.t.key);   // (key and mink are adjacent: the whole table in 16-byte stores)
+    SLR_K4_STOP_AT(1);                                   // (debug-hook builds: before the table clear since round 6)
+    // A. distinct values and their smallest column, as mf_match_binned_kernel; the four first probes are independent LDS atomics in
+    //    flight together, a collision continues in the loop
+    {
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4 e4 = {kEmpty, kEmpty, kEmpty, kEmpty};
+        u32x4 *const t4 = reinterpret_cast<u32x4 *>(sh.t.key);   // (key and mink are adjacent: the whole table in 16-byte stores)
 #pragma unroll
-            for (int q = 0; q < 2 * TS / 4 / BLOCK; q++) t4[tid + q * BLOCK] = e4;
-        }
-        __syncthreads();
+        for (int q = 0; q < 2 * TS / 4 / BLOCK; q++) t4[tid + q * BLOCK] = e4;
+    }
+    __syncthreads();
 #pragma unroll
-        for (int i = 0; i < IPT; i++) old[i] = cand[i] ? atomicCAS(&sh.t.key[slot[i]], kEmpty, bits[i]) : kEmpty;
+    for (int i = 0; i < IPT; i++) old[i] = cand[i] ? atomicCAS(&sh.t.key[slot[i]], kEmpty, bits[i]) : kEmpty;
 #pragma unroll
-        for (int i = 0; i < IPT; i++) {
-            if (cand[i]) {
-                unsigned h = slot[i], o = old[i];
-                while (o != kEmpty && o != bits[i]) {
-                    h = (h + 1) & (TS - 1);
-                    o = atomicCAS(&sh.t.key[h], kEmpty, bits[i]);
-                }
-                atomicMin(&sh.t.mink[h], (unsigned)(k0 + i));
-                slot[i] = h;
+    for (int i = 0; i < IPT; i++) {
+        if (cand[i]) {
+            unsigned h = slot[i], o = old[i];
+            while (o != kEmpty && o != bits[i]) {
+                h = (h + 1) & (TS - 1);
+                o = atomicCAS(&sh.t.key[h], kEmpty, bits[i]);
             }
+            atomicMin(&sh.t.mink[h], (unsigned)(k0 + i));
+            slot[i] = h;
         }
-        __syncthreads();
-        // representatives: the pixels that are their value's smallest column.  The key half of the table is dead already and
-        // becomes the bin counters (cnt[kBins + tid] = a sink for the thread's non-representatives: the atomics below are
-        // unconditional and independent, and never pile up on one address)
-        repmask = 0;
+    }
+    __syncthreads();
+    // representatives: the pixels that are their value's smallest column.  The key half of the table is dead already and
+    // becomes the bin counters (cnt[kBins + tid] = a sink for the thread's non-representatives: the atomics below are
+    // unconditional and independent, and never pile up on one address)
+    {
         unsigned mk4[IPT];
 #pragma unroll
         for (int i = 0; i < IPT; i++) mk4[i] = sh.t.mink[slot[i]];
@@ -599,47 +574,27 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == 1024 ? 8 : 4)) void mf_match_lean_
 #pragma unroll
         for (int i = 0; i < IPT; i++)
             if (cand[i] && mk4[i] == (unsigned)(k0 + i)) repmask |= 1u << i;
-        __syncthreads();                                 // the whole table is dead from here on
-    };
-    if constexpr (NOHASH) {
-#pragma unroll
-        for (int q = 0; q < kPer; q++) cnt[tid + q * BLOCK] = 0u;
-        __syncthreads();
-        SLR_K4_STOP_AT(1);
-    } else {
-        SLR_K4_STOP_AT(1);                               // (debug-hook builds: before the table clear since round 6)
-        hash_dedup();
     }
+    __syncthreads();                                     // the whole table is dead from here on
     SLR_K4_STOP_AT(2);
 
     // B. counting sort of the representatives by phase bin
     unsigned bin[IPT], rank[IPT];
     float2 *const pk = reinterpret_cast<float2 *>(sh.b.pk2);
-#pragma unroll 1
-    for (int pass = 0;; pass++) {
 #pragma unroll
-        for (int i = 0; i < IPT; i++) bin[i] = (repmask >> i) & 1u ? (unsigned)phase_bin(pr[i]) : (unsigned)(kBins + tid);
+    for (int i = 0; i < IPT; i++) bin[i] = (repmask >> i) & 1u ? (unsigned)phase_bin(pr[i]) : (unsigned)(kBins + tid);
 #pragma unroll
-        for (int i = 0; i < IPT; i++) rank[i] = atomicAdd(&cnt[bin[i]], 1u);
-        __syncthreads();
+    for (int i = 0; i < IPT; i++) rank[i] = atomicAdd(&cnt[bin[i]], 1u);
+    __syncthreads();
+    {
         unsigned c[kPer], sum = 0;
 #pragma unroll
-        for (int q = 0; q < kPer; q++) {
-            c[q] = cnt[tid * kPer + q]; sum += c[q];
-            if (NOHASH && c[q] > kHeavyBin) sum += 0x10000u;          // (the row's counts stay below 2^16: the heavy-bin count rides above them)
-        }
+        for (int q = 0; q < kPer; q++) { c[q] = cnt[tid * kPer + q]; sum += c[q]; }
         unsigned total;
         unsigned excl = wg_exclusive_scan<BLOCK>(sum, 0u, [](unsigned a, unsigned b) { return a + b; }, scan_tmp, &total);   // (its barrier: every thread has read its counters)
-        if (NOHASH && pass == 0 && (total >> 16) != 0u) {             // workgroup-uniform: some bin is heavy -> this row takes the dedup
-            __syncthreads();
-            hash_dedup();
-            continue;
-        }
-        excl &= 0xFFFFu; total &= 0xFFFFu;
 #pragma unroll
         for (int q = 0; q < kPer; q++) { sh.b.bs[1 + tid * kPer + q] = excl; excl += c[q]; }   // bs lies in the mink half
         if (tid == 0) { sh.b.bs[0] = 0u; sh.b.bs[kBins + 1] = total; sh.b.bs[kBins + 2] = total; }
-        break;
     }
     __syncthreads();
     {
@@ -814,563 +769,6 @@ __global__ __launch_bounds__(BLOCK, (BLOCK == 1024 ? 8 : 4)) void mf_match_lean_
     __builtin_nontemporal_store(hw, reinterpret_cast<unsigned *>(has + o));
     if (match_k) *reinterpret_cast<int4 *>(match_k + o) = make_int4(best[0], best[1], best[2], best[3]);
 }
-
-// ------------------------------------------------------------------------------------------------------
-// K4, lean form, PERSISTENT (round 5; the grouped launches of slr_reconstruct_mf_batch: no valid bytes, no match columns).
-// mf_match_lean_kernel<1024, ., true, ., .> with the rows of a launch walked by 2 resident workgroups per CU instead of one
-// workgroup per row: with the undistortion tables coming from L2 (frames grouped) the kernel is no longer waiting for HBM but for
-// its own VALU work (79 % busy) -- and for the 16 bytes per pixel of phases at the head of every row, which nothing overlapped
-// inside a workgroup.  Here a workgroup issues the loads of its NEXT row's phases (8 registers) before it starts on the current
-// one, so they arrive during ~13 us of index build and queries; the launch / argument-load / tail of 24000 short workgroups
-// goes as well.  Same arithmetic, same LDS layout, same results (tests/test_gpu_lean.py: == the per-row form, bit for bit).
-// Workgroup w runs on XCD w % 8 and takes the items q = w / 8, w / 8 + G / 8, ... of that XCD: item q = (row (q / nframes) * 8 + xcd,
-// frame q % nframes) -- a row of all frames on the same XCD, close in time, as in the per-row form.
-// ------------------------------------------------------------------------------------------------------
-#ifdef SLR_ALL_FORMS   // (measured: 105 against 76 us per frame; SLR_OPT_MF_MATCH_ALGO 7 exists in `make FORMS=all` builds only)
-template <bool HAS_T, bool TAME, bool X87>
-__global__ __launch_bounds__(1024, 8) void mf_match_lean_persist_kernel(const float *__restrict__ phaseL0, const float *__restrict__ phaseR0,
-                                                                        int W, int H, int row0, K4Lean kc,
-                                                                        const float4 *__restrict__ undL, const float *__restrict__ undRx,
-                                                                        float *__restrict__ xyz0, uint8_t *__restrict__ has0,
-                                                                        int nframes, size_t frame_px)
-{
-    constexpr int BLOCK = 1024, IPT = 4, N = BLOCK * IPT, TS = 2 * N, kPer = kBins / BLOCK;
-    constexpr unsigned kEmpty = 0xFFFFFFFFu;
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    __shared__ union {
-        struct { unsigned key[TS]; unsigned mink[TS]; } t;               // phase bits -> smallest column
-        struct { f32x4 pk2[N / 2 + 3]; unsigned bs[kBins + 3]; } b;      // pairs of (phi, column as bits) grouped by bin (+ sentinels, + a sink); bin index
-    } sh;
-    __shared__ unsigned scan_tmp[BLOCK / 64];
-    static_assert(sizeof(sh.b) <= sizeof(sh.t), "the index must fit the dead hash table (two workgroups per CU)");
-
-    const int tid = threadIdx.x, k0 = tid * IPT;
-    const bool inrow = k0 < W;                           // W % 4 == 0: a thread's 4 pixels are all inside or all outside
-    const int xcd = (int)blockIdx.x & 7, lw = (int)blockIdx.x >> 3, nl = (int)gridDim.x >> 3;
-    const int items = ((H - xcd + 7) / 8) * nframes;     // rows xcd, xcd + 8, ... of every frame
-    auto item_of = [&](int q, int &brow, size_t &fo) { brow = (q / nframes) * 8 + xcd; fo = (size_t)(q % nframes) * frame_px; };
-
-    // pr / pl: the current row's phases.  Each is re-loaded for the NEXT row right behind its last use in the current one (pr: the
-    // scatter of the pairs; pl: the queries) -- into the same registers, so the prefetch costs none (a second set of 8 spilled at
-    // the 64 registers of two 1024-thread workgroups per CU)
-    float pr[IPT] = {0, 0, 0, 0}, pl[IPT] = {0, 0, 0, 0};
-    if (lw < items && inrow) {
-        int brow; size_t fo;
-        item_of(lw, brow, fo);
-        load_f32_blocked<IPT>(phaseR0 + fo + (size_t)brow * W, k0, k0 + IPT, true, pr);
-        load_f32_blocked<IPT>(phaseL0 + fo + (size_t)brow * W, k0, k0 + IPT, true, pl);
-    }
-#pragma unroll 1
-    for (int q = lw; q < items; q += nl) {
-        int brow; size_t fo;
-        item_of(q, brow, fo);
-        float *const xyz = xyz0 + 3 * fo;
-        uint8_t *const has = has0 + fo;
-        const int row = brow + row0;
-        const size_t base = (size_t)brow * W, trow = (size_t)row * W;
-        const bool more = q + nl < items && inrow;
-        size_t nbase = 0;                                // the next item's row, as an offset into the phase arrays
-        if (more) { int nb; size_t nfo; item_of(q + nl, nb, nfo); nbase = nfo + (size_t)nb * W; }
-        {
-            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-            const u32x4 e4 = {kEmpty, kEmpty, kEmpty, kEmpty};
-            u32x4 *const t4 = reinterpret_cast<u32x4 *>(sh.t.key);   // (key and mink are adjacent: the whole table in 16-byte stores)
-#pragma unroll
-            for (int j = 0; j < 2 * TS / 4 / BLOCK; j++) t4[tid + j * BLOCK] = e4;
-        }
-        __syncthreads();
-
-        // A. distinct values and their smallest column (as mf_match_lean_kernel)
-        unsigned slot[IPT], bits[IPT], old[IPT];
-        bool cand[IPT];
-#pragma unroll
-        for (int i = 0; i < IPT; i++) {
-            bits[i] = __float_as_uint(pr[i]);
-            const bool ok = inrow && (pr[i] == pr[i]);               // NaN (= no phase) can never satisfy the predicate
-            const bool dup = i > 0 && ok && bits[i] == bits[i - 1];
-            cand[i] = ok && !dup;
-            slot[i] = (bits[i] * 2654435761u) >> (32 - __builtin_ctz(TS));
-        }
-#pragma unroll
-        for (int i = 0; i < IPT; i++) old[i] = cand[i] ? atomicCAS(&sh.t.key[slot[i]], kEmpty, bits[i]) : kEmpty;
-#pragma unroll
-        for (int i = 0; i < IPT; i++) {
-            if (cand[i]) {
-                unsigned h = slot[i], o = old[i];
-                while (o != kEmpty && o != bits[i]) {
-                    h = (h + 1) & (TS - 1);
-                    o = atomicCAS(&sh.t.key[h], kEmpty, bits[i]);
-                }
-                atomicMin(&sh.t.mink[h], (unsigned)(k0 + i));
-                slot[i] = h;
-            }
-        }
-        __syncthreads();
-        unsigned *const cnt = sh.t.key;                      // the key half is dead: bin counters (+ one sink per thread)
-        unsigned repmask = 0;
-        unsigned mk4[IPT];
-#pragma unroll
-        for (int i = 0; i < IPT; i++) mk4[i] = sh.t.mink[slot[i]];
-#pragma unroll
-        for (int j = 0; j < kPer; j++) cnt[tid + j * BLOCK] = 0u;
-#pragma unroll
-        for (int i = 0; i < IPT; i++)
-            if (cand[i] && mk4[i] == (unsigned)(k0 + i)) repmask |= 1u << i;
-        __syncthreads();                                     // the whole table is dead from here on
-
-        // B. counting sort of the representatives by phase bin
-        unsigned bin[IPT], rank[IPT];
-#pragma unroll
-        for (int i = 0; i < IPT; i++) bin[i] = (repmask >> i) & 1u ? (unsigned)phase_bin(pr[i]) : (unsigned)(kBins + tid);
-#pragma unroll
-        for (int i = 0; i < IPT; i++) rank[i] = atomicAdd(&cnt[bin[i]], 1u);
-        __syncthreads();
-        float2 *const pk = reinterpret_cast<float2 *>(sh.b.pk2);
-        {
-            unsigned c[kPer], sum = 0;
-#pragma unroll
-            for (int j = 0; j < kPer; j++) { c[j] = cnt[tid * kPer + j]; sum += c[j]; }
-            unsigned total;
-            unsigned excl = wg_exclusive_scan<BLOCK>(sum, 0u, [](unsigned a, unsigned b) { return a + b; }, scan_tmp, &total);
-#pragma unroll
-            for (int j = 0; j < kPer; j++) { sh.b.bs[1 + tid * kPer + j] = excl; excl += c[j]; }   // bs lies in the mink half
-            if (tid == 0) { sh.b.bs[0] = 0u; sh.b.bs[kBins + 1] = total; sh.b.bs[kBins + 2] = total; }
-        }
-        __syncthreads();
-        {
-            const unsigned total = sh.b.bs[kBins + 1];
-            if (tid < 4) pk[total + tid] = make_float2(__builtin_nanf(""), __uint_as_float(0xFFFFFFFFu));   // sentinels
-            unsigned st[IPT];
-#pragma unroll
-            for (int i = 0; i < IPT; i++) st[i] = sh.b.bs[1 + ((repmask >> i) & 1u ? bin[i] : (unsigned)kBins)];
-#pragma unroll
-            for (int i = 0; i < IPT; i++) {
-                const unsigned at = (repmask >> i) & 1u ? st[i] + rank[i] : (unsigned)N + 4u;
-                pk[at] = make_float2(pr[i], __uint_as_float((unsigned)(k0 + i)));
-            }
-        }
-        if (more) load_f32_blocked<IPT>(phaseR0 + nbase, k0, k0 + IPT, true, pr);     // the next row's right phases: in flight from here
-        __syncthreads();
-
-        // queries
-        int best[IPT];
-        unsigned qa[IPT], qe[IPT];
-#pragma unroll
-        for (int i = 0; i < IPT; i++) {
-            const bool act = inrow && pl[i] == pl[i];
-            const int b = phase_bin(pl[i]);
-            const unsigned i0 = sh.b.bs[b], i1 = sh.b.bs[b + 3];
-            qa[i] = (i0 & ~1u) * 8u;
-            qe[i] = act ? i1 * 8u : 0u;
-        }
-        const char *const pkb = reinterpret_cast<const char *>(sh.b.pk2);
-#pragma unroll
-        for (int i = 0; i < IPT; i++) {
-            unsigned bk = 0xFFFFFFFFu;
-            const float p = pl[i];
-            bool wide = false;
-            if constexpr (X87) wide = __ballot(qa[i] < qe[i] && !(fabsf(p) >= 0.25f)) != 0ull;      // (see mf_match_lean_kernel: Sterbenz)
-            if (X87 && wide) {
-                const double pd = (double)p;
-                for (unsigned a = qa[i]; a < qe[i]; a += 32u) {
-                    const f32x4 c0 = *reinterpret_cast<const f32x4 *>(pkb + a);
-                    const f32x4 c1 = *reinterpret_cast<const f32x4 *>(pkb + a + 16);
-                    const unsigned h0 = fabs(pd - (double)c0.x) < 0.1 ? __float_as_uint(c0.y) : 0xFFFFFFFFu;
-                    const unsigned h1 = fabs(pd - (double)c0.z) < 0.1 ? __float_as_uint(c0.w) : 0xFFFFFFFFu;
-                    const unsigned h2 = fabs(pd - (double)c1.x) < 0.1 ? __float_as_uint(c1.y) : 0xFFFFFFFFu;
-                    const unsigned h3 = fabs(pd - (double)c1.z) < 0.1 ? __float_as_uint(c1.w) : 0xFFFFFFFFu;
-                    bk = min(min(bk, h0), min(h1, min(h2, h3)));
-                }
-            } else {
-                for (unsigned a = qa[i]; a < qe[i]; a += 32u) {
-                    const f32x4 c0 = *reinterpret_cast<const f32x4 *>(pkb + a);
-                    const f32x4 c1 = *reinterpret_cast<const f32x4 *>(pkb + a + 16);
-                    const unsigned h0 = fabsf(p - c0.x) < 0.1f ? __float_as_uint(c0.y) : 0xFFFFFFFFu;
-                    const unsigned h1 = fabsf(p - c0.z) < 0.1f ? __float_as_uint(c0.w) : 0xFFFFFFFFu;
-                    const unsigned h2 = fabsf(p - c1.x) < 0.1f ? __float_as_uint(c1.y) : 0xFFFFFFFFu;
-                    const unsigned h3 = fabsf(p - c1.z) < 0.1f ? __float_as_uint(c1.w) : 0xFFFFFFFFu;
-                    bk = min(min(bk, h0), min(h1, min(h2, h3)));
-                }
-            }
-            best[i] = (int)bk;
-        }
-        __syncthreads();                                     // every wave is done with the index: the row's XYZ goes through its LDS
-
-        // triangulation (mfreconstruct.cpp:297-326), branch-free for the 4 pixels (as mf_match_lean_kernel)
-        const size_t tk0 = trow + (inrow ? k0 : 0);
-        const f32x4 ua = *reinterpret_cast<const f32x4 *>(undL + tk0 / 2);
-        const f32x4 ub = *(reinterpret_cast<const f32x4 *>(undL + tk0 / 2) + 1);
-        float urx[IPT];
-#pragma unroll
-        for (int i = 0; i < IPT; i++) urx[i] = undRx[trow + (inrow && best[i] >= 0 ? best[i] : 0)];
-        const float ulx[IPT] = {ua.x, ua.z, ub.x, ub.z}, uly[IPT] = {ua.y, ua.w, ub.y, ub.w};
-        float out[12];
-        unsigned hw = 0;
-        unsigned bad = 0;
-#pragma unroll
-        for (int i = 0; i < IPT; i++) {
-            const double r0 = (double)ulx[i] + kc.q3, r1 = (double)uly[i] + kc.q7, r2 = kc.q11;
-            const double w = kc.q14 * (X87 ? (double)ulx[i] - (double)urx[i] : (double)(float)(ulx[i] - urx[i])) + kc.q15;   // :299
-            auto expo = [](double x) -> unsigned { return ((unsigned)__double2hiint(x) >> 20) & 0x7FFu; };
-            if constexpr (TAME) {
-                const bool fin = __builtin_isfinite(ulx[i]) && __builtin_isfinite(uly[i]);
-                if (!(expo(w) - (1023u - 200u) < 400u && fin) && best[i] >= 0) bad |= 1u << i;
-            } else {
-                const unsigned e0 = expo(r0), e1 = expo(r1), e2 = expo(r2), e3 = expo(w);
-                const unsigned emin = min(min(e0, e1), min(e2, e3)), emax = max(max(e0, e1), max(e2, e3));
-                if (!(emin >= 1023u - 200u && emax < 1023u + 200u) && best[i] >= 0) bad |= 1u << i;
-            }
-            double y = __builtin_amdgcn_rcp(w);
-            y = __builtin_fma(y, __builtin_fma(-w, y, 1.0), y);
-            y = __builtin_fma(y, __builtin_fma(-w, y, 1.0), y);
-            const double r[3] = {r0, r1, r2};
-            float X[3];
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                const double qq = r[c] * y;
-                const double e = __builtin_fma(-w, qq, r[c]);
-                X[c] = (float)__builtin_fma(e, y, qq);
-            }
-            out[3 * i] = X[0]; out[3 * i + 1] = X[1]; out[3 * i + 2] = X[2];
-        }
-        if (__builtin_expect(bad != 0, 0)) {                 // exact zeros, w == 0, NaN, extreme exponents: the three real divisions
-#pragma unroll 1
-            for (int i = 0; i < IPT; i++) {
-                if (!((bad >> i) & 1u)) continue;
-                const double r0 = (double)ulx[i] + kc.q3, r1 = (double)uly[i] + kc.q7, r2 = kc.q11;
-                const double w = kc.q14 * (X87 ? (double)ulx[i] - (double)urx[i] : (double)(float)(ulx[i] - urx[i])) + kc.q15;
-                const float X0 = (float)(r0 / w), X1 = (float)(r1 / w), X2 = (float)(r2 / w);
-#pragma unroll
-                for (int j = 0; j < IPT; j++)
-                    if (j == i) { out[3 * j] = X0; out[3 * j + 1] = X1; out[3 * j + 2] = X2; }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < IPT; i++) {
-            if constexpr (HAS_T) {                           // matCoordTrans(3x4 f32) * [X;1]: f64 accumulate, narrow once
-                const double X0 = (double)out[3 * i], X1 = (double)out[3 * i + 1], X2 = (double)out[3 * i + 2];
-#pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    double s_ = __builtin_fma(kc.T[c * 4], X0, 0.0);
-                    s_ = __builtin_fma(kc.T[c * 4 + 1], X1, s_);
-                    s_ = __builtin_fma(kc.T[c * 4 + 2], X2, s_);
-                    out[3 * i + c] = (float)(s_ + kc.T[c * 4 + 3]);
-                }
-            }
-            const bool m = best[i] >= 0;
-            out[3 * i] = m ? out[3 * i] : 0.0f; out[3 * i + 1] = m ? out[3 * i + 1] : 0.0f; out[3 * i + 2] = m ? out[3 * i + 2] : 0.0f;
-            hw |= (m ? 1u : 0u) << (8 * i);
-        }
-        const f32x4 v0 = {out[0], out[1], out[2], out[3]}, v1 = {out[4], out[5], out[6], out[7]}, v2 = {out[8], out[9], out[10], out[11]};
-        {
-            f32x4 *const x4 = reinterpret_cast<f32x4 *>(&sh);
-            x4[3 * tid] = v0; x4[3 * tid + 1] = v1; x4[3 * tid + 2] = v2;
-            if (more) load_f32_blocked<IPT>(phaseL0 + nbase, k0, k0 + IPT, true, pl);     // ... and its left phases (behind the f64 work: registers)
-            __syncthreads();
-            f32x4 *const r4 = reinterpret_cast<f32x4 *>(xyz + 3 * base);
-            const int n4 = 3 * W / 4;                        // 16-byte words of the row
-#pragma unroll
-            for (int j = 0; j < 3; j++)
-                if (tid + j * BLOCK < n4) __builtin_nontemporal_store(x4[tid + j * BLOCK], r4 + tid + j * BLOCK);
-        }
-        if (inrow) __builtin_nontemporal_store(hw, reinterpret_cast<unsigned *>(has + base + k0));
-        __syncthreads();                                     // the exchange space is read: the next row clears the table
-    }
-}
-
-#ifdef SLR_ALL_FORMS   // (measured, not faster than the 1024 x 4 form: SLR_OPT_MF_MATCH_ALGO 5 / 6 exist in `make FORMS=all` builds only)
-#endif  // SLR_ALL_FORMS
-
-// ------------------------------------------------------------------------------------------------------
-// K4 (exact indexed form, lean, round 4): the same index as mf_match_lean_kernel -- hash dedup, representatives counting-sorted
-// into 0.25-wide bins, exact predicate on the window's pairs -- cut for instruction-level instead of wave-level parallelism:
-//   * 512 threads x 8 pixels (two runs of 4: columns 4t.. and 2048 + 4t.., so that a wave's global accesses keep the 1024-thread
-//     form's shape): a row is 8 waves instead of 16 (half the barrier population, an 8-wave DPP scan), a thread keeps 8
-//     independent LDS atomics / reads in flight where the 1024-thread form keeps 4;
-//   * TS (hash slots) = 8192 -> 64 KB, two rows per CU at up to 128 VGPRs; TS = 6144 -> 48 KB, THREE rows per CU at 80 VGPRs:
-//     three workgroups in different stages fill each other's barrier waits (the 1024-thread form is pinned to two by the
-//     CU's 32 wave slots).  A slot is (hash >> 16) * TS >> 16; linear probing wraps by compare;
-//   * the query reads the first 8 pairs of EVERY pixel's window unconditionally (4 ds_read_b128 per pixel, two pixels = 8 reads
-//     in flight, no loop-carried branch between them; 8 NaN sentinels close the array) -- 95 % of the windows of a scene's rows end there;
-//     a loop continues for the rest.  An inactive pixel queries with a NaN (never matches);
-//   * the exponent guard of the shared-reciprocal quotients looks at w only: r0 = ulx + q3 and r1 = uly + q7 are sums of a
-//     finite f32 and a host-checked double (K4Lean is only built when q3, q7, q11 are finite, not -0 and zero or within
-//     2^+-100), so they are zero or within 2^-152 .. 2^129 whenever the table entries are finite -- one v_cmp_class each;
-//   * the hash table is cleared with 16-byte stores.
-// Bit-equal to mf_match_lean_kernel / the general forms / the oracle (tests/test_gpu_lean.py, test_gpu_fullsize.py).
-// ------------------------------------------------------------------------------------------------------
-template <bool HAS_T, int TS, int WPS>
-__global__ __launch_bounds__(512, WPS) void mf_match_lean8_kernel(const float *__restrict__ phaseL, const uint8_t *__restrict__ validL,
-                                                              const float *__restrict__ phaseR, const uint8_t *__restrict__ validR,
-                                                              int W, int H, int row0, K4Lean kc, int stop,
-                                                              const float4 *__restrict__ undL, const float *__restrict__ undRx,
-                                                              float *__restrict__ xyz,
-                                                              uint8_t *__restrict__ has, int32_t *__restrict__ match_k)
-{
-    constexpr int BLOCK = 512, IPT = 8;
-    constexpr int N = BLOCK * IPT;                       // 4096 pixels
-    constexpr int kPer = kBins / BLOCK;                  // bins per thread
-    constexpr unsigned kEmpty = 0xFFFFFFFFu;             // a NaN pattern: never a candidate's phase bits
-    constexpr int kSent = 8;                             // NaN pairs behind the last candidate
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    static_assert(TS >= kBins + BLOCK && TS % (2 * BLOCK) == 0 && TS <= 65536, "bin counters live in the key half; 16-byte clears");
-    constexpr bool kPow2 = (TS & (TS - 1)) == 0;
-    __shared__ union {
-        struct { unsigned key[TS]; unsigned mink[TS]; } t;                         // phase bits -> smallest column
-        struct { f32x4 pk2[(N + kSent + 2) / 2]; unsigned bs[kBins + 3]; } b;      // (phi, column) pairs by bin + sentinels + a sink; bin index
-    } sh;
-    __shared__ unsigned scan_tmp[BLOCK / 64];
-    static_assert(sizeof(sh.b.pk2) >= (size_t)(kBins + BLOCK) * 4, "the bin index must not overlap the live bin counters");
-
-    const int row = blockIdx.x + row0, tid = threadIdx.x;
-    const size_t base = (size_t)blockIdx.x * W;
-    // a thread's 8 pixels are two runs of 4: columns [4 tid, 4 tid + 4) and [2048 + 4 tid, ...) -- every global access of a wave is
-    // then the 1024-thread form's (16 bytes per lane at a 16-byte stride in, 48 bytes per lane at a 48-byte stride out); 8
-    // CONSECUTIVE pixels per thread cost 86 instead of 11 us of stores (96-byte lane stride)
-    const int kg[2] = {4 * tid, N / 2 + 4 * tid};
-    const bool ing[2] = {kg[0] < W, kg[1] < W};          // W % 4 == 0: a run is all inside or all outside
-#define SLR_KCOL(i) (kg[(i) >> 2] + ((i) & 3))
-
-    float pr[IPT], pl[IPT];
-    unsigned vr[IPT], vl[IPT];
-#pragma unroll
-    for (int i = 0; i < IPT; i++) { pr[i] = 0.0f; pl[i] = 0.0f; vr[i] = 0u; vl[i] = 0u; }
-#pragma unroll
-    for (int g = 0; g < 2; g++)
-        if (ing[g]) {
-            load_f32_blocked<4>(phaseR + base, kg[g], kg[g] + 4, true, pr + 4 * g);
-            load_valid_blocked<4>(validR, base, kg[g], kg[g] + 4, true, vr + 4 * g);
-            load_f32_blocked<4>(phaseL + base, kg[g], kg[g] + 4, true, pl + 4 * g);
-            load_valid_blocked<4>(validL, base, kg[g], kg[g] + 4, true, vl + 4 * g);
-        }
-    const size_t trow = (size_t)row * W;
-    {
-        const u32x4 e4 = {kEmpty, kEmpty, kEmpty, kEmpty};
-        u32x4 *const t4 = reinterpret_cast<u32x4 *>(sh.t.key);
-#pragma unroll
-        for (int q = 0; q < 2 * TS / 4 / BLOCK; q++) t4[tid + q * BLOCK] = e4;
-    }
-    __syncthreads();
-    SLR_K4_STOP_AT(1);
-
-    // A. distinct values and their smallest column
-    unsigned slot[IPT], old[IPT];
-    unsigned candm = 0;
-#pragma unroll
-    for (int i = 0; i < IPT; i++) {
-        const unsigned bits = __float_as_uint(pr[i]);
-        const bool ok = ing[i >> 2] && vr[i] && (pr[i] == pr[i]);
-        const bool dup = (i & 3) > 0 && ok && vr[i - 1] && bits == __float_as_uint(pr[i - 1]);
-        candm |= (ok && !dup ? 1u : 0u) << i;
-        const unsigned h = bits * 2654435761u;
-        slot[i] = kPow2 ? h >> (32 - __builtin_ctz(TS)) : ((h >> 16) * (unsigned)TS) >> 16;
-    }
-#pragma unroll
-    for (int i = 0; i < IPT; i++) old[i] = (candm >> i) & 1u ? atomicCAS(&sh.t.key[slot[i]], kEmpty, __float_as_uint(pr[i])) : kEmpty;
-#pragma unroll
-    for (int i = 0; i < IPT; i++) {
-        if ((candm >> i) & 1u) {
-            const unsigned bits = __float_as_uint(pr[i]);
-            unsigned h = slot[i], o = old[i];
-            while (o != kEmpty && o != bits) {
-                h = kPow2 ? (h + 1) & (TS - 1) : (h + 1 == (unsigned)TS ? 0u : h + 1);
-                o = atomicCAS(&sh.t.key[h], kEmpty, bits);
-            }
-            atomicMin(&sh.t.mink[h], (unsigned)SLR_KCOL(i));
-            slot[i] = h;
-        }
-    }
-    __syncthreads();
-    unsigned *const cnt = sh.t.key;                      // the key half is dead: bin counters (+ one sink per thread)
-    unsigned repmask = 0;
-    {
-        unsigned mk[IPT];
-#pragma unroll
-        for (int i = 0; i < IPT; i++) mk[i] = sh.t.mink[slot[i]];
-        {
-            const u32x4 z4 = {0u, 0u, 0u, 0u};
-            u32x4 *const c4 = reinterpret_cast<u32x4 *>(cnt);
-#pragma unroll
-            for (int q = 0; q < kPer / 4; q++) c4[tid + q * BLOCK] = z4;
-            cnt[kBins + tid] = 0u;
-        }
-#pragma unroll
-        for (int i = 0; i < IPT; i++)
-            if (((candm >> i) & 1u) && mk[i] == (unsigned)SLR_KCOL(i)) repmask |= 1u << i;
-    }
-    __syncthreads();                                     // the whole table is dead from here on
-    SLR_K4_STOP_AT(2);
-
-    // B. counting sort of the representatives by phase bin
-    unsigned bin[IPT], rank[IPT];
-#pragma unroll
-    for (int i = 0; i < IPT; i++) bin[i] = (repmask >> i) & 1u ? (unsigned)phase_bin(pr[i]) : (unsigned)(kBins + tid);
-#pragma unroll
-    for (int i = 0; i < IPT; i++) rank[i] = atomicAdd(&cnt[bin[i]], 1u);
-    __syncthreads();
-    float2 *const pk = reinterpret_cast<float2 *>(sh.b.pk2);
-    {
-        unsigned c[kPer], sum = 0;
-        const u32x4 *const c4 = reinterpret_cast<const u32x4 *>(cnt + tid * kPer);
-#pragma unroll
-        for (int q = 0; q < kPer / 4; q++) {
-            const u32x4 v = c4[q];
-            c[4 * q] = v.x; c[4 * q + 1] = v.y; c[4 * q + 2] = v.z; c[4 * q + 3] = v.w;
-            sum += v.x + v.y + v.z + v.w;
-        }
-        unsigned total;
-        unsigned excl = wg_exclusive_scan<BLOCK>(sum, 0u, [](unsigned a, unsigned b) { return a + b; }, scan_tmp, &total);
-#pragma unroll
-        for (int q = 0; q < kPer; q++) { sh.b.bs[1 + tid * kPer + q] = excl; excl += c[q]; }
-        if (tid == 0) { sh.b.bs[0] = 0u; sh.b.bs[kBins + 1] = total; sh.b.bs[kBins + 2] = total; }
-    }
-    __syncthreads();
-    {
-        const unsigned total = sh.b.bs[kBins + 1];
-        if (tid < kSent) pk[total + tid] = make_float2(__builtin_nanf(""), __uint_as_float(0xFFFFFFFFu));   // sentinels
-        unsigned st[IPT];
-#pragma unroll
-        for (int i = 0; i < IPT; i++) st[i] = sh.b.bs[1 + ((repmask >> i) & 1u ? bin[i] : (unsigned)kBins)];
-#pragma unroll
-        for (int i = 0; i < IPT; i++) {
-            const unsigned at = (repmask >> i) & 1u ? st[i] + rank[i] : (unsigned)(N + kSent);   // (the sink)
-            pk[at] = make_float2(pr[i], __uint_as_float((unsigned)SLR_KCOL(i)));
-        }
-    }
-    __syncthreads();
-    SLR_K4_STOP_AT(4);
-
-    // queries: the reference's predicate on the pairs of bins [b-1, b+1] (and a few neighbours), smallest column wins
-    int best[IPT];
-    unsigned qa[IPT], qe[IPT];                           // byte offsets into pk: first 16-byte word, end of the window
-    float pq[IPT];
-#pragma unroll
-    for (int i = 0; i < IPT; i++) {
-        const bool act = ing[i >> 2] && vl[i] && pl[i] == pl[i];
-        const int b = phase_bin(pl[i]);                  // (a NaN lands in bin 0; it queries with a NaN and an empty window)
-        const unsigned i0 = sh.b.bs[b], i1 = sh.b.bs[b + 3];
-        qa[i] = (i0 & ~1u) * 8u;
-        qe[i] = act ? i1 * 8u : 0u;
-        pq[i] = act ? pl[i] : __builtin_nanf("");
-    }
-    const char *const pkb = reinterpret_cast<const char *>(sh.b.pk2);
-    auto hit4 = [](float p, const f32x4 &c0, const f32x4 &c1) -> unsigned {
-        const unsigned h0 = fabsf(p - c0.x) < 0.1f ? __float_as_uint(c0.y) : 0xFFFFFFFFu;
-        const unsigned h1 = fabsf(p - c0.z) < 0.1f ? __float_as_uint(c0.w) : 0xFFFFFFFFu;
-        const unsigned h2 = fabsf(p - c1.x) < 0.1f ? __float_as_uint(c1.y) : 0xFFFFFFFFu;
-        const unsigned h3 = fabsf(p - c1.z) < 0.1f ? __float_as_uint(c1.w) : 0xFFFFFFFFu;
-        return min(min(h0, h1), min(h2, h3));
-    };
-#pragma unroll
-    for (int i = 0; i < IPT; i += 2) {                   // two pixels' first 8 pairs each: 8 independent 16-byte reads
-        f32x4 c[2][4];
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) c[j][q] = *reinterpret_cast<const f32x4 *>(pkb + qa[i + j] + 16 * q);
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            unsigned bk = min(hit4(pq[i + j], c[j][0], c[j][1]), hit4(pq[i + j], c[j][2], c[j][3]));
-            for (unsigned a = qa[i + j] + 64u; a < qe[i + j]; a += 32u) {
-                const f32x4 d0 = *reinterpret_cast<const f32x4 *>(pkb + a);
-                const f32x4 d1 = *reinterpret_cast<const f32x4 *>(pkb + a + 16);
-                bk = min(bk, hit4(pq[i + j], d0, d1));
-            }
-            best[i + j] = (int)bk;                       // 0xFFFFFFFF == -1: no match
-        }
-    }
-    SLR_K4_STOP_AT5(best[0]);
-
-    // triangulation (mfreconstruct.cpp:297-326), branch-free, 4 pixels at a time.  All table reads before the first store (vmcnt
-    // counts stores too: a later run's loads would wait for an earlier run's stores to reach memory)
-    float urx[IPT];
-    f32x4 ul4[IPT / 2];
-#pragma unroll
-    for (int g = 0; g < IPT; g += 4) {
-        const bool in = ing[g >> 2];
-#pragma unroll
-        for (int i = 0; i < 4; i++) urx[g + i] = undRx[trow + (in && best[g + i] >= 0 ? best[g + i] : 0)];
-        const f32x4 *const u4 = reinterpret_cast<const f32x4 *>(undL + (trow + (in ? kg[g >> 2] : 0)) / 2);
-        ul4[g / 2] = u4[0]; ul4[g / 2 + 1] = u4[1];
-    }
-#pragma unroll
-    for (int g = 0; g < IPT; g += 4) {
-        const f32x4 ua = ul4[g / 2], ub = ul4[g / 2 + 1];
-        float out[12];
-        unsigned hw = 0;
-        const float ulx[4] = {ua.x, ua.z, ub.x, ub.z}, uly[4] = {ua.y, ua.w, ub.y, ub.w};
-        unsigned bad = 0;                                // pixels whose quotients need the real divisions
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const double r0 = (double)ulx[i] + kc.q3, r1 = (double)uly[i] + kc.q7, r2 = kc.q11;
-            const double w = kc.q14 * (double)(float)(ulx[i] - urx[g + i]) + kc.q15;
-            const unsigned ew = ((unsigned)__double2hiint(w) >> 20) & 0x7FFu;
-            const bool fin = __builtin_isfinite(ulx[i]) && __builtin_isfinite(uly[i]);
-            if (!(ew - (1023u - 200u) < 400u && fin) && best[g + i] >= 0) bad |= 1u << i;
-            double y = __builtin_amdgcn_rcp(w);          // the three IEEE quotients from one refined reciprocal (mf_match_lean_kernel)
-            y = __builtin_fma(y, __builtin_fma(-w, y, 1.0), y);
-            y = __builtin_fma(y, __builtin_fma(-w, y, 1.0), y);
-            const double r[3] = {r0, r1, r2};
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                const double q = r[c] * y;
-                const double e = __builtin_fma(-w, q, r[c]);
-                out[3 * i + c] = (float)__builtin_fma(e, y, q);
-            }
-        }
-#if defined(SLR_K4_ABL) && (SLR_K4_ABL & 4)
-        bad = 0;
-#endif
-        if (__builtin_expect(bad != 0, 0)) {             // w == 0, NaN, extreme exponents, non-finite table entries: the real divisions
-#pragma unroll 1
-            for (int i = 0; i < 4; i++) {
-                if (!((bad >> i) & 1u)) continue;
-                float ux = 0.0f, uy = 0.0f, ur = 0.0f;
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (j == i) { ux = ulx[j]; uy = uly[j]; ur = urx[g + j]; }
-                const double r0 = (double)ux + kc.q3, r1 = (double)uy + kc.q7, r2 = kc.q11;
-                const double w = kc.q14 * (double)(float)(ux - ur) + kc.q15;
-                const float X0 = (float)(r0 / w), X1 = (float)(r1 / w), X2 = (float)(r2 / w);
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (j == i) { out[3 * j] = X0; out[3 * j + 1] = X1; out[3 * j + 2] = X2; }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            if constexpr (HAS_T) {                       // matCoordTrans(3x4 f32) * [X;1]: f64 accumulate, narrow once
-                const double X0 = (double)out[3 * i], X1 = (double)out[3 * i + 1], X2 = (double)out[3 * i + 2];
-#pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    double s = __builtin_fma(kc.T[c * 4], X0, 0.0);
-                    s = __builtin_fma(kc.T[c * 4 + 1], X1, s);
-                    s = __builtin_fma(kc.T[c * 4 + 2], X2, s);
-                    out[3 * i + c] = (float)(s + kc.T[c * 4 + 3]);
-                }
-            }
-            const bool m = best[g + i] >= 0;
-            out[3 * i] = m ? out[3 * i] : 0.0f; out[3 * i + 1] = m ? out[3 * i + 1] : 0.0f; out[3 * i + 2] = m ? out[3 * i + 2] : 0.0f;
-            hw |= (m ? 1u : 0u) << (8 * i);
-        }
-#if defined(SLR_K4_ABL) && (SLR_K4_ABL & 1)
-        if (out[0] + out[5] + out[10] != 1.2345e-30f) continue;
-#endif
-        if (!ing[g >> 2]) continue;
-        const size_t o = base + kg[g >> 2];
-        f32x4 *d4 = reinterpret_cast<f32x4 *>(xyz + 3 * o);  // streaming output: non-temporal stores
-        const f32x4 v0 = {out[0], out[1], out[2], out[3]}, v1 = {out[4], out[5], out[6], out[7]}, v2 = {out[8], out[9], out[10], out[11]};
-        __builtin_nontemporal_store(v0, d4);
-        __builtin_nontemporal_store(v1, d4 + 1);
-        __builtin_nontemporal_store(v2, d4 + 2);
-        __builtin_nontemporal_store(hw, reinterpret_cast<unsigned *>(has + o));
-        if (match_k) *reinterpret_cast<int4 *>(match_k + o) = make_int4(best[g], best[g + 1], best[g + 2], best[g + 3]);
-    }
-#undef SLR_KCOL
-}
-
-#endif  // SLR_ALL_FORMS
 
 // K4 for rows wider than 4096 pixels.  The hash table of a whole 8192-pixel right row needs 128 KB of LDS (one 1024-thread
 // workgroup per CU, 8 pixels and too many registers per thread: 2.3x the time per pixel of a 4096-wide row).  "Smallest
@@ -1759,151 +1157,6 @@ __global__ __launch_bounds__(1024, 8) void mf_match_wide_kernel(const float *__r
     }
 }
 
-template <int BLOCK, int IPT>
-__global__ __launch_bounds__(BLOCK, (BLOCK == 1024 ? 8 : 4)) void mf_match_sorted_kernel(const float *__restrict__ phaseL, const uint8_t *__restrict__ validL,
-                                                              const float *__restrict__ phaseR, const uint8_t *__restrict__ validR,
-                                                              int W, int H, int row0, DevCalib cal, int vec_ok,
-                                                              const float2 *__restrict__ undL, const float *__restrict__ undRx,
-                                                              float *__restrict__ xyz,
-                                                              uint8_t *__restrict__ has, int32_t *__restrict__ match_k)
-{
-    constexpr int N = BLOCK * IPT;
-    typedef rocprim::block_radix_sort<unsigned, BLOCK, IPT> Sort;  // keys only: (group << 16) | k
-    __shared__ union {
-        typename Sort::storage_type sort;
-        struct { float2 pk[N]; } d;                      // distinct values: (phi, min column as bits)
-    } sh;
-    __shared__ float phR[N];                             // right-row phases, gathered by column after the sort
-    __shared__ int scan_tmp[BLOCK / 64];
-    __shared__ unsigned last_key[BLOCK];
-    __shared__ int n_distinct;
-    __shared__ unsigned short binfirst[kBins + 1];
-    __shared__ unsigned chunk_min[BLOCK];
-    __shared__ unsigned scanu_tmp[BLOCK / 64];
-
-    const int row = blockIdx.x + row0, tid = threadIdx.x;   // absolute image row (row0: first row of a band)
-    const size_t base = (size_t)blockIdx.x * W;
-    const int k0 = tid * IPT;
-    const bool vec = (vec_ok & 1) != 0;
-    const int stop = vec_ok >> 8;                        // debug: leave after phase N (SLR_DEBUG_K4_STOP), 0 = run all
-
-    // all row loads of this thread are issued here, before the sort, and are independent of each other
-    float pr[IPT], pl[IPT];
-    unsigned vr[IPT], vl[IPT];
-    load_f32_blocked<IPT>(phaseR + base, k0, W, vec, pr);
-    load_valid_blocked<IPT>(validR, base, k0, W, vec, vr);
-    load_f32_blocked<IPT>(phaseL + base, k0, W, vec, pl);
-    load_valid_blocked<IPT>(validL, base, k0, W, vec, vl);
-
-    // Sort key: any function of phi works for correctness (equal phases share a key, and the stable order keeps
-    // ascending k inside a key).  16 bits = 12-bit bin + 4-bit hash of the value: two 8-bit radix passes instead
-    // of four, and the result is already grouped by bin for the candidate index below.  Distinct values that
-    // collide on a key merely produce a few extra run heads.
-    unsigned keys[IPT];
-#pragma unroll
-    for (int i = 0; i < IPT; i++) {                      // blocked arrangement: stable order == ascending k
-        const bool ok = (k0 + i < W) && vr[i] && (pr[i] == pr[i]);   // NaN can never satisfy the predicate
-        const unsigned b = __float_as_uint(pr[i]);
-        const unsigned h4 = (b ^ (b >> 4) ^ (b >> 8) ^ (b >> 12) ^ (b >> 16) ^ (b >> 20)) & 0xFu;
-        keys[i] = ok ? ((((unsigned)phase_bin(pr[i]) << 4) | h4) << 16) | (unsigned)(k0 + i) : 0xFFFFFFFFu;
-        phR[k0 + i] = pr[i];
-    }
-    SLR_K4_STOP_AT(1);
-    Sort().sort(keys, sh.sort, 16, 32);
-    __syncthreads();                                     // phR visible; everybody is done with sh.sort
-    SLR_K4_STOP_AT(2);
-    unsigned phb[IPT];                                   // phase bits of the sorted items (0xFFFFFFFF = none)
-#pragma unroll
-    for (int i = 0; i < IPT; i++) phb[i] = keys[i] != 0xFFFFFFFFu ? __float_as_uint(phR[keys[i] & 0xFFFFu]) : 0xFFFFFFFFu;
-    last_key[tid] = phb[IPT - 1];
-    __syncthreads();
-    unsigned prev = tid ? last_key[tid - 1] : 0xFFFFFFFFu;
-    int heads = 0;
-    unsigned headmask = 0;
-#pragma unroll
-    for (int i = 0; i < IPT; i++) {
-        const bool h = phb[i] != 0xFFFFFFFFu && phb[i] != prev;      // run head: value differs from its predecessor
-        prev = phb[i];
-        headmask |= h ? (1u << i) : 0u;
-        heads += h ? 1 : 0;
-    }
-    int total;
-    int pos = wg_exclusive_scan<BLOCK>(heads, 0, [](int a, int b) { return a + b; }, scan_tmp, &total);
-#pragma unroll
-    for (int i = 0; i < IPT; i++)
-        if (headmask & (1u << i)) { sh.d.pk[pos] = make_float2(__uint_as_float(phb[i]), __uint_as_float(keys[i] & 0xFFFFu)); pos++; }
-    if (tid == 0) n_distinct = total;
-    for (int b = tid; b <= kBins; b += BLOCK) binfirst[b] = 0xFFFFu;
-    __syncthreads();
-    const int nd = n_distinct;
-    SLR_K4_STOP_AT(3);
-
-    // Bin index over the distinct values: bin(phi) = clamp(floor((phi + 512) * 4)) is monotone and two values
-    // closer than 0.1001 land at most one bin apart, so bins [b-1, b+1] of phiL hold a superset of its
-    // candidates.  binfirst[b] = first distinct index whose bin is >= b (suffix-min fill), binfirst[kBins] = nd.
-    for (int i = tid; i < nd; i += BLOCK) {
-        const int b = phase_bin(sh.d.pk[i].x);
-        if (i == 0 || phase_bin(sh.d.pk[i - 1].x) != b) binfirst[b] = (unsigned short)i;
-    }
-    __syncthreads();
-    {
-        constexpr int kPer = kBins / BLOCK;              // bins per thread (kBins is a multiple of BLOCK)
-        unsigned m = 0xFFFFu;
-#pragma unroll
-        for (int q = kPer - 1; q >= 0; q--) { const unsigned v = binfirst[tid * kPer + q]; m = v < m ? v : m; }
-        chunk_min[tid] = m;                              // min over this thread's bins
-        __syncthreads();
-        // exclusive suffix-min over threads = exclusive prefix-min in reversed thread order
-        // (0xFFFF is the identity here: the bins' first indices are 16-bit)
-        unsigned carry = wg_exclusive_scan<BLOCK>(chunk_min[BLOCK - 1 - tid], 0xFFFFu, [](unsigned a, unsigned b) { return a < b ? a : b; },
-                                                  scanu_tmp, (unsigned *)nullptr);
-        __syncthreads();
-        chunk_min[BLOCK - 1 - tid] = carry;
-        __syncthreads();
-        carry = chunk_min[tid];
-        carry = carry < (unsigned)nd ? carry : (unsigned)nd;     // nothing later -> end sentinel
-#pragma unroll
-        for (int q = kPer - 1; q >= 0; q--) {
-            const unsigned v = binfirst[tid * kPer + q];
-            carry = v < carry ? v : carry;
-            binfirst[tid * kPer + q] = (unsigned short)carry;
-        }
-        if (tid == 0) binfirst[kBins] = (unsigned short)nd;
-    }
-    __syncthreads();
-
-    SLR_K4_STOP_AT(4);
-    // queries: exact reference predicate over the <= 3-bin candidate window, smallest column wins
-    int best[IPT];
-    int qi0[IPT], qi1[IPT];
-#pragma unroll
-    for (int i = 0; i < IPT; i++) {                      // all window bounds first: independent LDS reads
-        const bool act = k0 + i < W && vl[i] && pl[i] == pl[i];
-        const int b = act ? phase_bin(pl[i]) : 0;
-        qi0[i] = binfirst[b > 0 ? b - 1 : 0];
-        qi1[i] = act ? (int)binfirst[b + 2 < kBins ? b + 2 : kBins] : 0;
-    }
-#pragma unroll
-    for (int i = 0; i < IPT; i++) {
-        unsigned bk = 0xFFFFFFFFu;
-        for (int idx = qi0[i]; idx < qi1[i]; idx += 4) {     // 4 candidates per round trip (8-byte (phi, k) pairs)
-            float2 c[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) c[q] = sh.d.pk[idx + q < N ? idx + q : N - 1];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const bool hit = idx + q < qi1[i] && phase_match(pl[i], c[q].x, cal.eval_x87);
-                const unsigned kk = hit ? __float_as_uint(c[q].y) : 0xFFFFFFFFu;
-                bk = kk < bk ? kk : bk;
-            }
-        }
-        best[i] = bk == 0xFFFFFFFFu ? -1 : (int)bk;
-    }
-
-    SLR_K4_STOP_AT5(best[0]);
-    k4_emit<IPT>(best, base, k0, row, W, vec, cal, undL, undRx, xyz, has, match_k);
-}
-
 
 // Utilities::undistortPoints depends only on the pixel position and the camera, so its 5 f64 fixed-point
 // iterations (utilities.cpp:83-91) are evaluated once per (calibration, image size) into tables -- bit-identical
@@ -1931,12 +1184,13 @@ hipError_t launch_undistort_tables(const DevCalib &cal, int W, int H, float *und
 }
 
 // algo: 0 = auto (lean binned form when it applies, else the general binned form, the chunked form for wide rows, the sweep
-// beyond), 1 = sweep, 2 = sorted indexed form, 3 = general binned indexed form
+// beyond), 1 = sweep, 3 = general binned indexed form, 4 = the lean form without the LDS-transposed stores, 8 = the lean form
+// where it applies (= auto there)
 // can launch_mf_match take several frames in one launch (the lean 1024-thread kernel on aligned rows of 2049..4096 pixels)?
 bool mf_match_batches_frames(const float *phaseL, const float *phaseR, const float *xyz, const uint8_t *has, int W, const DevCalib &cal,
                              int algo, const float *undL_xy, const float *undRx, size_t frame_px)
 {
-    return (algo == 0 || algo == 4 || algo == 7 || algo == 8 || algo == 9) && undL_xy && undRx && cal.q_simple && W > 2048 && W <= 4096 && W % 4 == 0 &&
+    return (algo == 0 || algo == 4 || algo == 8) && undL_xy && undRx && cal.q_simple && W > 2048 && W <= 4096 && W % 4 == 0 &&
            (uintptr_t)undL_xy % 16 == 0 && (uintptr_t)phaseL % 16 == 0 && (uintptr_t)phaseR % 16 == 0 && (uintptr_t)xyz % 16 == 0 &&
            (uintptr_t)has % 4 == 0 && frame_px % 4 == 0;
 }
@@ -1957,24 +1211,11 @@ hipError_t launch_mf_match(const float *phaseL, const uint8_t *validL, const flo
         const int vec_ok = (k4_stop << 8) | (int)((W % 4 == 0) && ((uintptr_t)phaseL % 16 == 0) && ((uintptr_t)phaseR % 16 == 0) &&
                            ((uintptr_t)validL % 4 == 0) && ((uintptr_t)validR % 4 == 0) && ((uintptr_t)xyz % 16 == 0) &&
                            ((uintptr_t)has % 4 == 0) && (!match_k || (uintptr_t)match_k % 16 == 0));
-    // (the sorted form, algo 2, is measured-dominated by the binned one: compiled with -DSLR_ALL_FORMS only)
-#ifdef SLR_ALL_FORMS
-#define SLR_SORTED(BLOCK, IPT)                                                                                     \
-    do {                                                                                                           \
-        if (algo == 2)                                                                                             \
-            SLR_LAUNCH((mf_match_sorted_kernel<BLOCK, IPT>), dim3(H), dim3(BLOCK), 0, s, phaseL, validL,   \
-                               phaseR, validR, W, H, row0, cal, vec_ok, undL, undRx, xyz, has, match_k);           \
-        else                                                                                                       \
-            SLR_LAUNCH((mf_match_binned_kernel<BLOCK, IPT>), dim3(H), dim3(BLOCK), 0, s, phaseL, validL,   \
-                               phaseR, validR, W, H, row0, cal, vec_ok, undL, undRx, xyz, has, match_k);           \
-    } while (0)
-#else
-#define SLR_SORTED(BLOCK, IPT)                                                                                     \
+#define SLR_BINNED(BLOCK, IPT)                                                                                     \
     SLR_LAUNCH((mf_match_binned_kernel<BLOCK, IPT>), dim3(H), dim3(BLOCK), 0, s, phaseL, validL, phaseR, validR, W, H, row0, cal, \
                vec_ok, undL, undRx, xyz, has, match_k)
-#endif
         // the usual call (aligned rows of 513..1024 or 2049..4096 pixels, tables, stereoRectify's Q): the lean kernel
-        if ((algo == 0 || (algo >= 4 && algo <= 9)) && (vec_ok & 1) && undL && undRx && cal.q_simple && ((W > 512 && W <= 1024) || (W > 2048 && W <= 4096)) &&
+        if ((algo == 0 || algo == 4 || algo == 8) && (vec_ok & 1) && undL && undRx && cal.q_simple && ((W > 512 && W <= 1024) || (W > 2048 && W <= 4096)) &&
             (uintptr_t)undL % 16 == 0 && ((size_t)W * sizeof(float2)) % 16 == 0) {
             K4Lean kc;
             kc.q3 = cal.Q[3]; kc.q7 = cal.Q[7]; kc.q11 = cal.Q[11]; kc.q14 = cal.Q[14]; kc.q15 = cal.Q[15];
@@ -1990,76 +1231,19 @@ hipError_t launch_mf_match(const float *phaseL, const uint8_t *validL, const flo
         else { if (x87) SLR_LEAN1(BLOCK, false, true); else SLR_LEAN1(BLOCK, false, false); }                                     \
     } while (0)
             // round 4, rows of 2049..4096 pixels: algo 0 = 1024 threads x 4 pixels with the row's XYZ stored through LDS (whole
-            // kilobytes per store instruction: 86 vs 91 us in the batch); 4 = the same without the exchange (round 2); 5 / 6 = 512
-            // threads x 8 pixels with two / three rows per CU (measured: 98 / 94 us, not faster; their quotient guard needs a tame Q)
+            // kilobytes per store instruction: 86 vs 91 us in the batch); 4 = the same without the exchange (round 2)
             auto tame = [](double q, bool zero_ok) {
                 return (q == 0.0 && zero_ok && !signbit(q)) || (isfinite(q) && fabs(q) >= 0x1p-100 && fabs(q) <= 0x1p100);
             };
             const bool q_tame = tame(kc.q3, true) && tame(kc.q7, true) && tame(kc.q11, false);
-#ifdef SLR_ALL_FORMS
-            if (W > 2048 && (algo == 5 || algo == 6) && q_tame && !x87) {
-#define SLR_LEAN8(TS, WPS)                                                                                                       \
-    do {                                                                                                                         \
-        if (cal.has_T) SLR_LAUNCH((mf_match_lean8_kernel<true, TS, WPS>), dim3(H), dim3(512), 0, s, phaseL, validL, phaseR, validR, \
-                                  W, H, row0, kc, k4_stop, undL4, undRx, xyz, has, match_k);                                     \
-        else SLR_LAUNCH((mf_match_lean8_kernel<false, TS, WPS>), dim3(H), dim3(512), 0, s, phaseL, validL, phaseR, validR,        \
-                        W, H, row0, kc, k4_stop, undL4, undRx, xyz, has, match_k);                                               \
-    } while (0)
-                if (algo == 5) SLR_LEAN8(8192, 4); else SLR_LEAN8(6144, 6);
-#undef SLR_LEAN8
-                return hipGetLastError();
-            }
-#endif
-#ifdef SLR_ALL_FORMS
-            if (W > 2048 && algo == 7 && nframes > 1 && !validL && !validR && !match_k && k4_stop == 0) {
-                // round 5: the grouped launch as a PERSISTENT kernel (two resident workgroups per CU walk the rows, the next row's
-                // phases prefetched).  Measured (profiles/exp/r05/k4_persist_ab.txt): 105 us per frame against 77 for the per-row
-                // launch -- SLR_OPT_MF_MATCH_ALGO = 7 only, never picked by auto
-                static DevSlots cus_of;
-                int dev = 0;
-                (void)hipGetDevice(&dev);
-                int cus = cus_of.get(dev);
-                if (!cus) {
-                    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-                    cus_of.put(dev, cus);
-                }
-                const long long items = (long long)((H + 7) / 8) * 8 * nframes;
-                unsigned pg = (unsigned)(2 * cus) & ~7u;          // two 1024-thread workgroups per CU, whole groups of 8 (XCDs)
-                if ((long long)pg > items) pg = (unsigned)((items + 7) / 8 * 8);
-#define SLR_LEANP(T_, TAME_, X_) SLR_LAUNCH((mf_match_lean_persist_kernel<T_, TAME_, X_>), dim3(pg), dim3(1024), 0, s, phaseL, phaseR, W, H, row0, kc, \
-                                            undL4, undRx, xyz, has, nframes, frame_px)
-#define SLR_LEANP2(T_, TAME_) do { if (x87) SLR_LEANP(T_, TAME_, true); else SLR_LEANP(T_, TAME_, false); } while (0)
-                if (cal.has_T) { if (q_tame) SLR_LEANP2(true, true); else SLR_LEANP2(true, false); }
-                else { if (q_tame) SLR_LEANP2(false, true); else SLR_LEANP2(false, false); }
-#undef SLR_LEANP2
-#undef SLR_LEANP
-                return hipGetLastError();
-            }
-#endif
             if (W > 2048 && algo != 4) {                     // 1024 x 4 with the row's XYZ stored through LDS (round 4)
-                // round 6: SLR_OPT_MF_MATCH_ALGO 9 (FORMS=all builds) = the index WITHOUT the hash dedup (heavy rows rebuilt with it inside the
-                // kernel).  Measured on the bench's frames: 90 us against 81 with the dedup -- the reference's integer-quotient atan
-                // quantises the phases so hard that a row of 4064 valid pixels holds ~1500 distinct values, some of them 100-300 times
-                // (profiles/exp/r06/k4_nohash.txt): every row is "heavy", the dedup is doing real work.  Kept for phases that are not
-                // quantised like that; never picked by auto.
-#ifdef SLR_ALL_FORMS
-                const bool nohash = algo == 9;
-#else
-                constexpr bool nohash = false;
-#endif
-#define SLR_LEANX3(T_, TAME_, X_, N_) SLR_LAUNCH((mf_match_lean_kernel<1024, T_, true, TAME_, X_, N_>), dim3(grid), dim3(1024), 0, s, phaseL, validL, phaseR, validR, \
+#define SLR_LEANX2(T_, TAME_, X_) SLR_LAUNCH((mf_match_lean_kernel<1024, T_, true, TAME_, X_>), dim3(grid), dim3(1024), 0, s, phaseL, validL, phaseR, validR, \
                                       W, H, row0, kc, k4_stop, undL4, undRx, xyz, has, match_k, nframes, frame_px)
-#ifdef SLR_ALL_FORMS
-#define SLR_LEANX2(T_, TAME_, X_) do { if (nohash) SLR_LEANX3(T_, TAME_, X_, true); else SLR_LEANX3(T_, TAME_, X_, false); } while (0)
-#else
-#define SLR_LEANX2(T_, TAME_, X_) do { (void)nohash; SLR_LEANX3(T_, TAME_, X_, false); } while (0)
-#endif
 #define SLR_LEANX(T_, TAME_) do { if (x87) SLR_LEANX2(T_, TAME_, true); else SLR_LEANX2(T_, TAME_, false); } while (0)
                 if (cal.has_T) { if (q_tame) SLR_LEANX(true, true); else SLR_LEANX(true, false); }
                 else { if (q_tame) SLR_LEANX(false, true); else SLR_LEANX(false, false); }
 #undef SLR_LEANX
 #undef SLR_LEANX2
-#undef SLR_LEANX3
                 return hipGetLastError();
             }
             if (W <= 1024) SLR_LEAN(256); else SLR_LEAN(1024);
@@ -2069,14 +1253,11 @@ hipError_t launch_mf_match(const float *phaseL, const uint8_t *validL, const flo
         }
         if (nframes > 1) return hipErrorInvalidValue;
         // wide rows: 1024 threads x few pixels each -> 16 waves per row hide the serial LDS chains of a thread
-        if (W <= 256) SLR_SORTED(256, 1);
-        else if (W <= 512) SLR_SORTED(256, 2);
-        else if (W <= 1024) SLR_SORTED(256, 4);
-        else if (W <= 2048) SLR_SORTED(1024, 2);
-        else if (W <= 4096) SLR_SORTED(1024, 4);
-#ifdef SLR_ALL_FORMS
-        else if (algo == 2) SLR_SORTED(1024, 8);
-#endif
+        if (W <= 256) SLR_BINNED(256, 1);
+        else if (W <= 512) SLR_BINNED(256, 2);
+        else if (W <= 1024) SLR_BINNED(256, 4);
+        else if (W <= 2048) SLR_BINNED(1024, 2);
+        else if (W <= 4096) SLR_BINNED(1024, 4);
         else if ((algo == 0) && (vec_ok & 1) && undL && undRx && cal.q_simple && W <= 8192 && (uintptr_t)undL % 16 == 0 &&
                  ((size_t)W * sizeof(float2)) % 16 == 0) {   // rows of 4097 .. 8192 pixels (config 5): the whole right row in one index (round 5)
             K4Lean kc;
@@ -2096,7 +1277,7 @@ hipError_t launch_mf_match(const float *phaseL, const uint8_t *validL, const flo
         else                                                 // wider rows: the right row in chunks of 4096 columns
             SLR_LAUNCH(mf_match_chunked_kernel, dim3(H), dim3(1024), 0, s, phaseL, validL, phaseR, validR, W, H, row0,
                                cal, vec_ok, undL, undRx, xyz, has, match_k, (const int *)nullptr);
-#undef SLR_SORTED
+#undef SLR_BINNED
         return hipGetLastError();
     }
     if (algo != 1 && W <= 4096 * 8) {                       // up to 32768 columns: up to 8 chunks

@@ -1191,7 +1191,7 @@ static int mf_batch_group_of(const slr_ctx *c, int W, int rectify, int H = 0, co
     // (the pointer-dependent half of mf_match_batches_frames too, when the caller's outputs are known: a group whose match launch
     //  would be refused must not cost a group's phase scratch -- 0.8 GB at the default group, kept for the context's lifetime)
     const bool outs_ok = !xyz || ((uintptr_t)xyz % 16 == 0 && (uintptr_t)has % 4 == 0 && ((size_t)W * (size_t)H) % 4 == 0);
-    const bool match_groups = (c->opt_mf_match_algo == 0 || c->opt_mf_match_algo == 4 || c->opt_mf_match_algo == 7 || c->opt_mf_match_algo == 8 || c->opt_mf_match_algo == 9) && c->cal.q_simple && W > 2048 && W <= 4096 && W % 4 == 0 && outs_ok;
+    const bool match_groups = (c->opt_mf_match_algo == 0 || c->opt_mf_match_algo == 4 || c->opt_mf_match_algo == 8) && c->cal.q_simple && W > 2048 && W <= 4096 && W % 4 == 0 && outs_ok;
     if (match_groups) return c->opt_mf_batch_group;
     const int dg = rectify && dma_form_wanted(c, 0, 1) ? c->opt_mf_decode_group : 1;
     return dg < c->opt_mf_batch_group ? dg : c->opt_mf_batch_group;
@@ -2148,12 +2148,8 @@ int slr_set_option(slr_ctx *c, int option, int value)
     switch (option) {
         case SLR_OPT_MF_MATCH_ALGO:
             if (value < 0 || value > 9) return fail(c, SLR_ERR_INVALID_ARG, "SLR_OPT_MF_MATCH_ALGO must be 0..9");
-#ifndef SLR_ALL_FORMS
-            if (value == 2) return fail(c, SLR_ERR_UNSUPPORTED, "SLR_OPT_MF_MATCH_ALGO = 2 (sorted form) is compiled with -DSLR_ALL_FORMS only");
-            if (value == 5 || value == 6) return fail(c, SLR_ERR_UNSUPPORTED, "SLR_OPT_MF_MATCH_ALGO = 5 / 6 (512 x 8 shapes) are compiled with -DSLR_ALL_FORMS only");
-            if (value == 7) return fail(c, SLR_ERR_UNSUPPORTED, "SLR_OPT_MF_MATCH_ALGO = 7 (persistent grouped K4) is compiled with -DSLR_ALL_FORMS only");
-            if (value == 9) return fail(c, SLR_ERR_UNSUPPORTED, "SLR_OPT_MF_MATCH_ALGO = 9 (lean K4 without the hash dedup) is compiled with -DSLR_ALL_FORMS only");
-#endif
+            if (value == 2 || value == 5 || value == 6 || value == 7 || value == 9)
+                return fail(c, SLR_ERR_UNSUPPORTED, "SLR_OPT_MF_MATCH_ALGO = 2, 5, 6, 7, 9 are retired forms");
             c->opt_mf_match_algo = value;
             return SLR_OK;
         case SLR_OPT_MF_DECODE_VEC:
@@ -2163,16 +2159,12 @@ int slr_set_option(slr_ctx *c, int option, int value)
             return SLR_OK;
         case SLR_OPT_RECT_DECODE_ALGO:
             if (value < 0 || value > 7) return fail(c, SLR_ERR_INVALID_ARG, "SLR_OPT_RECT_DECODE_ALGO must be 0..7");
-#ifndef SLR_ALL_FORMS
-            if (value >= 2 && value <= 4) return fail(c, SLR_ERR_UNSUPPORTED, "SLR_OPT_RECT_DECODE_ALGO = 2, 3, 4 are compiled with -DSLR_ALL_FORMS only");
-#endif
+            if (value >= 2 && value <= 4) return fail(c, SLR_ERR_UNSUPPORTED, "SLR_OPT_RECT_DECODE_ALGO = 2, 3, 4 are retired forms");
             c->opt_rect_algo = value;
             return SLR_OK;
         case SLR_OPT_RECT_DMA_SHAPE:
             if (value < 0 || value > 6) return fail(c, SLR_ERR_INVALID_ARG, "SLR_OPT_RECT_DMA_SHAPE must be 0..6");
-#ifndef SLR_ALL_FORMS
-            if (value == 2 || value >= 4) return fail(c, SLR_ERR_UNSUPPORTED, "SLR_OPT_RECT_DMA_SHAPE = 2, 4, 5, 6 are compiled with -DSLR_ALL_FORMS only");
-#endif
+            if (value == 2 || value >= 4) return fail(c, SLR_ERR_UNSUPPORTED, "SLR_OPT_RECT_DMA_SHAPE = 2, 4, 5, 6 are retired forms");
             if (value != c->opt_dma_shape) {
                 c->opt_dma_shape = value;
                 SLR_TRY(use_device(c));

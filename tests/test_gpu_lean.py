@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import bits_equal, calib_parts, forms, np_of
+from util import bits_equal, calib_parts, np_of
 
 pytestmark = pytest.mark.gpu
 BLACK = 40
@@ -34,7 +34,7 @@ def test_k4_lean_vs_general_and_oracle(ctx, slr, oracle, synth, W, H, with_T, q)
     phL[1 % H, 9] = np.nan; phR[1 % H, 11] = np.nan
     exyz, ehas, emk = oracle.mf_triangulate(phL, vL, phR, vR, camL, camR, Q, T)
     try:
-        for algo in forms(ctx, slr, slr.capi.OPT_MF_MATCH_ALGO, (0, 3, 2, 4, 5, 6, 8, 9), required=(0, 3, 4, 8)):   # lean (auto), general binned, sorted (FORMS=all), the lean shapes, 8 = lean with the hash dedup (= auto), 9 = without it (FORMS=all)
+        for algo in (0, 3, 4, 8):                       # lean (auto), general binned, lean with per-thread stores, 8 = the lean kernel by name (= auto)
             ctx.set_option(slr.capi.OPT_MF_MATCH_ALGO, algo)
             xyz, has, mk = ctx.mf_triangulate(phL, vL, phR, vR)
             assert bits_equal(mk, emk) and bits_equal(has, ehas) and bits_equal(xyz, exyz), (W, algo)
@@ -45,10 +45,10 @@ def test_k4_lean_vs_general_and_oracle(ctx, slr, oracle, synth, W, H, with_T, q)
 
 @pytest.mark.parametrize("W,with_T,x87", [(4096, False, False), (2052, True, False), (4096, True, True)])
 def test_k4_lean_index_without_the_hash_light_and_heavy_rows(ctx, slr, oracle, synth, W, with_T, x87):
-    """round 6: the lean K4's index with and without the hash dedup (SLR_OPT_MF_MATCH_ALGO 9, FORMS=all builds).  Rows whose fullest
-    0.25-wide bin holds exactly 32 / 33 / many more right pixels (the no-hash form's in-kernel switch to the dedup is at > 32),
-    duplicates that are not neighbours, duplicates across thread boundaries, an all-equal row, an empty row: every form == the
-    general binned kernel == the oracle, bit for bit"""
+    """round 6: rows built for the lean K4's index without the hash dedup (SLR_OPT_MF_MATCH_ALGO 9, since retired), matched by the
+    lean K4 with it.  Rows whose fullest 0.25-wide bin holds exactly 32 / 33 / many more right pixels (the retired form switched to
+    the dedup at > 32), duplicates that are not neighbours, duplicates across thread boundaries, an all-equal row, an empty row:
+    every form == the general binned kernel == the oracle, bit for bit"""
     rng = np.random.default_rng(W)
     H = 8
     calib, _ = synth.make_calibration(max(W, 8), 8, with_T=with_T)
@@ -73,7 +73,7 @@ def test_k4_lean_index_without_the_hash_light_and_heavy_rows(ctx, slr, oracle, s
         ctx.set_option(slr.capi.OPT_EVAL_MODEL, 1)
     try:
         exyz, ehas, emk = oracle.mf_triangulate_ev(phL, vL, phR, vR, camL, camR, Q, x87, T)
-        for algo in forms(ctx, slr, slr.capi.OPT_MF_MATCH_ALGO, (0, 8, 3, 9), required=(0, 8, 3)):
+        for algo in (0, 8, 3):
             ctx.set_option(slr.capi.OPT_MF_MATCH_ALGO, algo)
             xyz, has, mk = ctx.mf_triangulate(phL, vL, phR, vR)
             assert bits_equal(mk, emk) and bits_equal(has, ehas) and bits_equal(xyz, exyz), (W, algo)
@@ -195,16 +195,12 @@ def test_gray_dma_form(dma_ctx, slr, oracle, synth, W, H, sw, sh, rows, resident
         ex, ey, ev = _gray_expect(oracle, raw, mxn, mfn, nc, nr, 3, sw, sh)
         dev = st[cam].cuda()
         ran = 0
-        for shape in forms(ctx, slr, slr.capi.OPT_RECT_DMA_SHAPE, (1, 3, 4, 5), default=3, required=(1, 3)):
+        for shape in (1, 3):
             ctx.set_option(slr.capi.OPT_RECT_DMA_SHAPE, shape)
             ctx.set_option(slr.capi.OPT_RECT_DECODE_ALGO, 7)                    # strict: an error if the form does not run
             ctx.set_rectify_maps(cam, mxn, mfn)
-            try:
-                cx, cy, v = ctx.gray_decode(dev, nc, nr, BLACK, 3, sw, sh, rectify_cam=cam)
-                ctx.synchronize()
-            except slr.capi.SlrError as e:                                      # a corner tile's box exceeds a 256-thread shape
-                assert e.status == slr.capi.ERR_UNSUPPORTED and shape in (4, 5), (shape, str(e))
-                continue
+            cx, cy, v = ctx.gray_decode(dev, nc, nr, BLACK, 3, sw, sh, rectify_cam=cam)
+            ctx.synchronize()
             assert bits_equal(np_of(cx), ex) and bits_equal(np_of(v), ev), (cam, shape)
             if rows:
                 assert bits_equal(np_of(cy), ey), (cam, shape)
@@ -262,19 +258,11 @@ def test_mf_batch_frame_groups_equal_frame_by_frame(ctx, slr, synth, W, H, frame
             x, h = ctx.reconstruct_mf_batch(stack, BLACK, True)
             ctx.synchronize()
             res[group] = (x.clone(), h.clone())
-        # SLR_OPT_MF_MATCH_ALGO 7: the grouped match launch as the persistent kernel (round 5, opt-in: measured slower)
-        ctx.set_option(slr.capi.OPT_MF_BATCH_GROUP, 8)
-        ctx.set_option(slr.capi.OPT_MF_BATCH_DECODE_GROUP, 8)
-        if 7 in forms(ctx, slr, slr.capi.OPT_MF_MATCH_ALGO, (7,)):       # (`make FORMS=all` builds only)
-            ctx.set_option(slr.capi.OPT_MF_MATCH_ALGO, 7)
-            x, h = ctx.reconstruct_mf_batch(stack, BLACK, True)
-            ctx.synchronize()
-            res["persist"] = (x.clone(), h.clone())
     finally:
         ctx.set_option(slr.capi.OPT_MF_MATCH_ALGO, 0)
         ctx.set_option(slr.capi.OPT_MF_BATCH_GROUP, 8)
         ctx.set_option(slr.capi.OPT_MF_BATCH_DECODE_GROUP, 8)
-    for group in [g for g in (2, 4, 8, 8 + 256, 3, 8 + 512, "persist") if g in res]:
+    for group in (2, 4, 8, 8 + 256, 3, 8 + 512):
         assert torch.equal(res[group][0].view(torch.int32), res[1][0].view(torch.int32)) and torch.equal(res[group][1], res[1][1]), group
     x0, h0 = ctx.reconstruct_mf(stack[0, 0], stack[0, 1], BLACK, True)
     ctx.synchronize()

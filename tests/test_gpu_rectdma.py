@@ -6,11 +6,11 @@ import numpy as np
 import pytest
 import torch
 
-from util import bits_equal, forms, np_of
+from util import bits_equal, np_of
 
 pytestmark = pytest.mark.gpu
 BLACK = 40
-SHAPES = tuple(range(7))         # 256x16/512 threads, 256x8/512, 256x8/256, 128x16/512, 128x8/256, 256x4/256, 128x16/256
+SHAPES = (0, 1, 3)               # 256x16/512 threads, 256x8/512, 128x16/512 (2, 4, 5, 6 are retired)
 
 
 def _expect(oracle, raw, mx, mf):
@@ -43,8 +43,7 @@ def test_dma_form_every_shape_and_depth(dma_ctx, slr, oracle, synth, W, H, stren
         eph, ev = _expect(oracle, raw, mxn, mfn)
         dev = st[cam].cuda()
         ran = 0
-        shapes = forms(ctx, slr, slr.capi.OPT_RECT_DMA_SHAPE, SHAPES, default=3, required=(0, 1, 3))   # (2, 4, 5, 6: FORMS=all builds)
-        for shape in shapes:
+        for shape in SHAPES:
             _opts(ctx, slr, 7, shape, 1)
             ctx.set_rectify_maps(cam, mxn, mfn)
             try:
@@ -58,7 +57,7 @@ def test_dma_form_every_shape_and_depth(dma_ctx, slr, oracle, synth, W, H, stren
                 ran += 1
             except slr.capi.SlrError as e:                                      # a strong map: some tile's box exceeds this shape
                 assert e.status == slr.capi.ERR_UNSUPPORTED and strength > 1.0, (shape, str(e))
-        assert ran >= min(4, len(shapes)), ran
+        assert ran >= min(4, len(SHAPES)), ran
 
 
 def test_dma_form_borders_on_every_side(dma_ctx, slr, oracle, synth):
@@ -74,7 +73,7 @@ def test_dma_form_borders_on_every_side(dma_ctx, slr, oracle, synth):
         mx, mf = synth.identity_maps(W, H, dx=dx, dy=dy, fx=fx, fy=fy)
         mxn, mfn = mx.numpy(), mf.numpy()
         eph, ev = _expect(oracle, raw, mxn, mfn)
-        for shape in forms(ctx, slr, slr.capi.OPT_RECT_DMA_SHAPE, SHAPES, default=3, required=(0, 1, 3)):
+        for shape in SHAPES:
             _opts(ctx, slr, 7, shape, 1 + shape % 2)
             ctx.set_rectify_maps(0, mxn, mfn)
             ph, v = ctx.mf_decode(dev, BLACK, rectify_cam=0)
@@ -101,7 +100,7 @@ def test_dma_form_many_tiles_per_workgroup_and_whole_path(dma_ctx, slr, oracle, 
     camL, camR, Q, T = calib_parts(oracle, calib)
     exyz, ehas, _ = oracle.mf_triangulate(exp[0][0], exp[0][1], exp[1][0], exp[1][1], camL, camR, Q, T)
     dev = st.cuda()
-    for shape in forms(ctx, slr, slr.capi.OPT_RECT_DMA_SHAPE, SHAPES, default=3, required=(0, 1, 3)):
+    for shape in SHAPES:
         for depth in (1, 2):
             _opts(ctx, slr, 7, shape, depth)
             for cam in range(2):
@@ -160,20 +159,15 @@ def test_dma_form_fullsize_every_shape(dma_ctx, slr, oracle, synth):
     torch.cuda.synchronize()
     exp = [_expect(oracle, st[cam].cpu().numpy(), maps[cam][0].cpu().numpy(), maps[cam][1].cpu().numpy()) for cam in range(2)]
     ran = []
-    have = forms(ctx, slr, slr.capi.OPT_RECT_DMA_SHAPE, SHAPES, default=3, required=(0, 1, 3))
-    for shape, depth in [(0, 1), (1, 1), (2, 1), (3, 1), (4, 1), (5, 1), (6, 1), (0, 2), (1, 2), (3, 2), (4, 2)]:
-        if shape not in have: continue
+    for shape, depth in [(0, 1), (1, 1), (3, 1), (0, 2), (1, 2), (3, 2)]:
         _opts(ctx, slr, 7, shape, depth)
         for cam in range(2):
             ctx.set_rectify_maps(cam, maps[cam][0], maps[cam][1])
-        try:
-            for cam in range(2):
-                ph, v = ctx.mf_decode(st[cam], BLACK, rectify_cam=cam)
-                ctx.synchronize()
-                assert bits_equal(np_of(v), exp[cam][1]) and bits_equal(np_of(ph), exp[cam][0]), (shape, depth, cam)
-            ran.append((shape, depth))
-        except slr.capi.SlrError as e:       # the 256-thread shapes hold few source rows: these maps' corner tiles may not fit
-            assert e.status == slr.capi.ERR_UNSUPPORTED and shape not in (0, 1, 3), (shape, str(e))
+        for cam in range(2):
+            ph, v = ctx.mf_decode(st[cam], BLACK, rectify_cam=cam)
+            ctx.synchronize()
+            assert bits_equal(np_of(v), exp[cam][1]) and bits_equal(np_of(ph), exp[cam][0]), (shape, depth, cam)
+        ran.append((shape, depth))
     assert (0, 1) in ran and (1, 1) in ran and (3, 2) in ran and len(ran) >= 6, ran
 
 

@@ -140,7 +140,9 @@ const char  *slr_last_error(const slr_ctx *ctx);
  * mode.  slr_mfn_rectify_decode (config 5): bit 0 = the per-pixel gather form, bit 1 = the register-staged tile form (as for the
  * u8 decodes: no digest / no buffer form), and two bits of its own: bit 7 = 512 threads x 2 pixels instead of 256 x 4 in the LDS-DMA
  * form, bit 8 = its ring of 4 plane groups (two workgroups per CU) instead of 3.  slr_fuse_voxels:
- * bit 9 = count the insert pass's atomics (slr_fuse_last_stats).  SLR_OPT_DEBUG_K4_STOP exists only in -DSLR_DEBUG_HOOKS builds of the library (phase ablation of the match kernel; outputs are not written). */
+ * bit 9 = count the insert pass's atomics (slr_fuse_last_stats).  slr_reconstruct_mf_batch / slr_reconstruct_hybrid_batch: bit 10 = the
+ * grouped LDS-DMA fused decode takes ONE frame per visit of a tile (instead of decoding each tile for all frames of a camera in the
+ * group back to back, with its tap setup and digest fetch once per visit).  SLR_OPT_DEBUG_K4_STOP exists only in -DSLR_DEBUG_HOOKS builds of the library (phase ablation of the match kernel; outputs are not written). */
 #define SLR_OPT_DEBUG_RECT_RESIDENT 8
 #define SLR_OPT_DEBUG_FLAGS 9
 #define SLR_OPT_DEBUG_K4_STOP 10

@@ -86,6 +86,7 @@ class FuseStats(C.Structure):
 
 
 DEBUG_FUSE_COUNT_ATOMICS = 512  # SLR_OPT_DEBUG_FLAGS bit 9: slr_fuse_voxels counts its insert pass's atomics (fuse_last_stats)
+DEBUG_ONE_FRAME_VISITS = 1024   # SLR_OPT_DEBUG_FLAGS bit 10: the grouped fused decode takes one frame per visit of a tile
 
 MODE_GRAY, MODE_GE, MODE_MF = 0, 1, 2
 ASSIGN_CYCLIC, ASSIGN_BLOCKED = 0, 1          # frame -> context assignment of the one-process multi-GPU entries (slr.h)

@@ -416,6 +416,13 @@ struct DmaJob {
     uint8_t *valid;              // null: the flag is folded into the phase (NaN), see launch_mf_decode
 };
 struct DmaJobs { DmaJob j[kDmaMaxJobs]; };   // the cameras of one frame, or of a group of frames (slr_reconstruct_mf_batch): j[2 f + cam]
+// VISITS.  In a group launch the frames of a camera share its boxes and digest: everything a workgroup derives from them for an
+// entry -- the digest fetch, dma_tap_setup (class, quad bases, read mode, tap selectors and weights), the ticket and the box of the
+// next entry -- does not depend on the frame.  So a workgroup of a visit job (camera, set of up to kDmaMaxVisit frames of the group)
+// decodes each entry it draws for all frames of its set back to back: a UNIT is the 7 phases of one (entry, frame), consecutive units
+// rotate the LDS buffers as consecutive tiles did, the plane DMAs issued ahead into the next unit read the next frame's stack, and
+// only the first frame of a visit sets the taps up, only the last one draws the next ticket and fetches the next digest.
+constexpr int kDmaMaxVisit = kDmaMaxJobs / 2;
 
 // LDS-DMA of 16 bytes per lane: LDS[lds_dst + 16 * lane] = buffer[voff + soff .. + 15] (zeros beyond the descriptor's range).
 // M0 carries the LDS base and is compiler-reserved: saved and restored inside the one statement that uses it.
@@ -637,11 +644,14 @@ __device__ __forceinline__ void dma_differences(int mode, const DmaTap tap[PX], 
 // are issued at the start of the NEXT tile's phase 0, a whole phase before the following wait, and a wave that still has
 // one of them outstanding there merely waits a little longer.
 constexpr int kDmaDigestPhase = 3;    // the phase of a tile in which the NEXT tile's digest is fetched (the next tile is known from phase 2 on)
+// digest = false: the unit of phase p fetches no digest (a frame of a visit other than its last, see DmaDecode).  The phases counted
+// are p - A + 1 .. p - 1; they reach back into the previous unit only beyond phase 7 - A > kDmaDigestPhase, so the digest phase in
+// the window is always the current unit's.
 template <int PX, int A, int PLANE_DMAS = 2>
-__device__ __host__ constexpr int dma_wait_count(int p)
+__device__ __host__ constexpr int dma_wait_count(int p, bool digest = true)
 {
     int n = 0;
-    for (int j = 1; j < A; j++) { const int ph = ((p - A + j) % 7 + 7) % 7; n += PLANE_DMAS + (ph == kDmaDigestPhase ? PX / 4 : 0); }
+    for (int j = 1; j < A; j++) { const int ph = ((p - A + j) % 7 + 7) % 7; n += PLANE_DMAS + (digest && ph == kDmaDigestPhase ? PX / 4 : 0); }
     return n;
 }
 
@@ -820,7 +830,8 @@ struct DmaDecode {
     static constexpr int TAP_WT = WT_OFF;
     static constexpr int LUT_OFF = WT_OFF + WT_BYTES;
     static constexpr int TKT_OFF = LUT_OFF + (kLutWords + 1) * 4;        // the next tile's ticket (wave 0 -> everybody)
-    static constexpr int LDS_BYTES = TKT_OFF + 12;
+    static constexpr int FRM_OFF = (TKT_OFF + 12 + 15) & ~15;            // the frames of a visit: stack and phase base per frame
+    static constexpr int LDS_BYTES = FRM_OFF + 16 * kDmaMaxVisit;
     static_assert(WT_OFF <= 65536 && LDS_BYTES <= 160 * 1024, "DMA destinations are 16-bit LDS addresses (M0)");
     static constexpr int kSentinel = kDmaSentinel;
 
@@ -834,6 +845,9 @@ struct DmaDecode {
     unsigned pstride, fringe_skip;
     int W, H, black_thr;
     DmaSched sc;                         // schedule (see "dynamic tile schedule")
+    // the visit (see VISITS): frame fk of the fn frames of the workgroup's set is decoded in the current unit (wave-uniform)
+    int fk, fn;
+    unsigned stack_bytes;
     // per-tile state
     DmaTap tap[PX];
     unsigned qbase[PX / 4];              // LDS address of the 8-byte window of each quad (read modes 0 and 1)
@@ -905,6 +919,19 @@ struct DmaDecode {
             dma16(voff, rs_dig, lds0 + (unsigned)(DIG_OFF + r * NT * 16) + wave_off, 0u);
         }
     }
+    __device__ __forceinline__ bool last_frame() const { return fk + 1 >= fn; }
+    // frame k of the visit: its stack (which = 0) or its phase image (which = 1), from the table the kernel's start put in LDS (read
+    // and waited for in one statement: a scalar load of the kernel arguments could still be in flight under the counted LDS waits)
+    __device__ __forceinline__ __amdgpu_buffer_rsrc_t frame_rsrc(int k, int which) const
+    {
+        unsigned long long v;
+        asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(lds0 + (unsigned)(FRM_OFF + 16 * k + 8 * which)) : "memory");
+        // (readfirstlane returns int: the low word must not be sign-extended into the high one)
+        const unsigned long long p = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)v) |
+                                     (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(v >> 32)) << 32;
+        return __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)p, 0, which ? (int)((unsigned)W * (unsigned)H * 4u) : (int)stack_bytes,
+                                                 0x00020000);
+    }
 
     static __device__ __forceinline__ float pair_q24(int Pa, int Pb) { return dma_pair_q24(Pa, Pb); }
     static __device__ __forceinline__ float finish_q24(float Fa, float Fb)
@@ -913,25 +940,48 @@ struct DmaDecode {
         else return dma_finish_q24(Fa, Fb);
     }
 
+    // the counted wait at the top of phase P: a unit that is not the last of its visit has fetched no digest in phase kDmaDigestPhase
+    template <int P>
+    __device__ __forceinline__ void unit_wait(bool last) const
+    {
+        constexpr int n = dma_wait_count<PX, A, PLANE_DMAS>(P), n0 = dma_wait_count<PX, A, PLANE_DMAS>(P, false);
+        if (plane_wave) {
+            if constexpr (n == n0) wait_vm<n>();
+            else if (last) wait_vm<n>();
+            else wait_vm<n0>();
+        } else if (P == 0) wait_vm<0>();   // (its share of the tile's digest, issued four phases ago)
+    }
+    // behind the barrier of phase P: the schedule (ticket, next digest: the last unit of a visit only) and the DMAs of phase P + A,
+    // which belong to the next unit from phase 7 - A on -- the next frame of the visit (same entry, same box) or the next entry
+    template <int K0, int P>
+    __device__ __forceinline__ void unit_schedule(bool last, unsigned voff_cur)
+    {
+        if (P == 1 && last) sc.draw();                                // (scalar memory: invisible to the counted vmcnt waits)
+        if constexpr (P == 2) { if (last) sc.pick_up(); }             // the ticket wave 0 drew in phase 1 -> the next tile
+        if (P == kDmaDigestPhase && last) issue_digest((unsigned)sc.nxt, sc.has_next);
+        if (P == 7 - A && fn > 1) rs_stack = frame_rsrc(last ? 0 : fk + 1, 0);
+        issue_planes((P + A) % 7, (K0 + P + A) % D, P + A >= 7 && last ? sc.voff_next : voff_cur);
+    }
+
     // phase P of a tile whose phase 0 uses LDS buffer K0.  voff_cur: this thread's chunk of the current tile's box.
     template <int K0, int P>
     __device__ __forceinline__ void phase(int ty, int tx, unsigned voff_cur)
     {
         static_assert(7 - A > 2 && kDmaDigestPhase > 2 && kDmaDigestPhase < 7, "the next tile is known from phase 2 on");
-        if (plane_wave) wait_vm<dma_wait_count<PX, A, PLANE_DMAS>(P)>();
-        else if (P == 0) wait_vm<0>();   // (its share of the tile's digest, issued four phases ago)
+        const bool last = last_frame();
+        unit_wait<P>(last);
 #if !defined(SLR_DMA_ABL) || SLR_DMA_ABL != 3
         asm volatile("s_barrier" ::: "memory");
 #endif
-        if (P == 1) sc.draw();                                        // (scalar memory: invisible to the counted vmcnt waits)
-        if constexpr (P == 2) sc.pick_up();                           // the ticket wave 0 drew in phase 1 -> the next tile
-        if (P == kDmaDigestPhase) issue_digest((unsigned)sc.nxt, sc.has_next);
-        issue_planes((P + A) % 7, (K0 + P + A) % D, P + A >= 7 ? sc.voff_next : voff_cur);
+        unit_schedule<K0, P>(last, voff_cur);
         if constexpr (P == 0) {
             if (out_pending) flush();
-            // tap state of the tile's pixels from the digest, and the wave's read mode for the tile
-            const unsigned *dg = reinterpret_cast<const unsigned *>(smem + DIG_OFF + threadIdx.x * (PX * 4));
-            mode = dma_tap_setup<PX, RS, TAP_WT, WT1_OFF>(smem, lds0, dg, tap, qbase, second, oslot);
+            if (fn > 1) rs_phase = frame_rsrc(fk, 1);                // (the flush above stored the previous unit's frame)
+            // tap state of the tile's pixels from the digest, and the wave's read mode for the tile: once per visit
+            if (fk == 0) {
+                const unsigned *dg = reinterpret_cast<const unsigned *>(smem + DIG_OFF + threadIdx.x * (PX * 4));
+                mode = dma_tap_setup<PX, RS, TAP_WT, WT1_OFF>(smem, lds0, dg, tap, qbase, second, oslot);
+            }
             ok = 0;
         }
         constexpr unsigned img0 = (unsigned)(((K0 + P) % D) * 2 * PS), img1 = img0 + PS;
@@ -967,7 +1017,7 @@ struct DmaDecode {
         else dma_differences<PX, img0, img1, (unsigned)RS>(mode, tap, qbase, second, sd);
         __builtin_amdgcn_s_setprio(0);
 #endif
-        if (P == 1) sc.publish();                                     // (the ticket has had the tap loop to arrive)
+        if (P == 1 && last) sc.publish();                             // (the ticket has had the tap loop to arrive)
         if constexpr (P == 0) {
 #pragma unroll
             for (int q = 0; q < PX; q++) {                         // computeShadows :198-204
@@ -1005,15 +1055,12 @@ struct DmaDecode {
     template <int K0, int P>
     __device__ __forceinline__ void idle_phase(unsigned voff_cur)
     {
-        if (plane_wave) wait_vm<dma_wait_count<PX, A, PLANE_DMAS>(P)>();
-        else if (P == 0) wait_vm<0>();
+        const bool last = last_frame();
+        unit_wait<P>(last);
         asm volatile("s_barrier" ::: "memory");
-        if (P == 1) sc.draw();
-        if constexpr (P == 2) sc.pick_up();
-        if (P == kDmaDigestPhase) issue_digest((unsigned)sc.nxt, sc.has_next);
-        issue_planes((P + A) % 7, (K0 + P + A) % D, P + A >= 7 ? sc.voff_next : voff_cur);
-        if constexpr (P == 0) { if (out_pending) flush(); out_pending = false; }
-        if (P == 1) sc.publish();
+        unit_schedule<K0, P>(last, voff_cur);
+        if constexpr (P == 0) { if (out_pending) flush(); out_pending = false; }     // (rs_phase: the frame of the unit flushed)
+        if (P == 1 && last) sc.publish();
     }
 
     template <int K0>
@@ -1056,8 +1103,10 @@ constexpr int mf_dma_waves() { return dma_waves_per_simd<LDS_BYTES, NT>() > 6 ? 
 template <int TW, int TH, int NT, int A, bool HASVALID, bool X87 = false>
 __global__ __launch_bounds__(NT, (HASVALID ? 4 : mf_dma_waves<DmaDecode<TW, TH, NT, A, HASVALID>::LDS_BYTES, NT>())) SLR_TICKET_KERNEL
 void mf_rect_decode_dma_kernel(DmaJobs jobs, int njobs, int pitch, int W, int H, int black_thr, const float *__restrict__ lut_g,
-                               int tiles_x, int tiles_y, unsigned *__restrict__ sched)
+                               int tiles_x, int tiles_y, unsigned *__restrict__ sched, int nsets, int nframes)
 {
+    // njobs: visit jobs.  nsets = 0: job ji is jobs.j[ji], one frame per visit.  nsets > 0: the jobs are the 2 nsets (camera, set)
+    // pairs of a group of g = nframes frames, job ji = camera ji & 1 of frames f0 .. f1 - 1 (the sets as even as g allows), see VISITS
     typedef DmaDecode<TW, TH, NT, A, HASVALID, X87> Dec;
     typedef DmaGeom<TW, TH, NT> Gm;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -1079,17 +1128,30 @@ void mf_rect_decode_dma_kernel(DmaJobs jobs, int njobs, int pitch, int W, int H,
         *reinterpret_cast<unsigned *>(smem + Dec::WT1_OFF + 4u * i) = w1;
     }
     __syncthreads();
-    if (!HASVALID && threadIdx.x == 0)                      // the undefined wrapped phase (n == d == 0: lutR -> S = 9, s = 0, sgn 0)
-        reinterpret_cast<int *>(lut)[kLutP + (9 << 8)] = Dec::kSentinel;
-    __syncthreads();
     // workgroup -> (XCD band, camera, index in the pool): the hardware deals workgroups round-robin to the XCDs, so bits 0-2 are the
     // band; the cameras ALTERNATE over the workgroups of a band.  (Round 2 gave the first half of the grid to camera 0.  The
     // workgroups of a persistent kernel keep the age they were launched with and the SIMDs favour older waves: the first third
     // of the grid runs its tiles in ~6 us, the last third in ~8 us -- so camera 0's tiles were gone after 100 us and camera 1's
     // after 130.  With the cameras interleaved and the tiles drawn by ticket, both pools are served by the same mix.)
-    const unsigned nblk = gridDim.x / (unsigned)njobs;      // workgroups per camera (a multiple of 8)
+    const unsigned nblk = gridDim.x / (unsigned)njobs;      // workgroups per (visit) job (a multiple of 8)
     const int xcd = (int)(blockIdx.x & 7u), nbx = (int)(nblk >> 3);
-    const int ji = (int)((blockIdx.x >> 3) % (unsigned)njobs), lb = (int)((blockIdx.x >> 3) / (unsigned)njobs);
+    const int vi = (int)((blockIdx.x >> 3) % (unsigned)njobs), lb = (int)((blockIdx.x >> 3) / (unsigned)njobs);
+    int ji = vi;                                            // the job of the visit's first frame
+    d.fk = 0; d.fn = 1;
+    if (nsets > 0) {
+        const int s = vi >> 1, f0 = s * nframes / nsets, f1 = (s + 1) * nframes / nsets;
+        ji = 2 * f0 + (vi & 1);
+        d.fn = f1 - f0;
+        if (threadIdx.x == 0)
+            for (int k = 0; k < d.fn; k++) {                // (wave-uniform indices: scalar loads of the kernel arguments)
+                unsigned long long *t = reinterpret_cast<unsigned long long *>(smem + Dec::FRM_OFF + 16 * k);
+                t[0] = (unsigned long long)(uintptr_t)jobs.j[ji + 2 * k].base;
+                t[1] = (unsigned long long)(uintptr_t)jobs.j[ji + 2 * k].phase;
+            }
+    }
+    if (!HASVALID && threadIdx.x == 0)                      // the undefined wrapped phase (n == d == 0: lutR -> S = 9, s = 0, sgn 0)
+        reinterpret_cast<int *>(lut)[kLutP + (9 << 8)] = Dec::kSentinel;
+    __syncthreads();
     const int T = tiles_x * tiles_y;
     d.sc.pool = DmaPool::of(T, (int)jobs.j[ji].entries, xcd);
     int cur = d.sc.pool.entry(xcd, lb);
@@ -1122,12 +1184,13 @@ void mf_rect_decode_dma_kernel(DmaJobs jobs, int njobs, int pitch, int W, int H,
 #endif
     // the schedule: the first tile by index, the others by ticket (tickets count from the band's nbx-th tile)
     d.pstride = jobs.j[ji].pstride; d.fringe_skip = jobs.j[ji].fringe_skip;
+    d.stack_bytes = jobs.j[ji].stack_bytes;
     d.rs_stack = __builtin_amdgcn_make_buffer_rsrc((void *)jobs.j[ji].base, 0, (int)jobs.j[ji].stack_bytes, 0x00020000);
     d.rs_dig = __builtin_amdgcn_make_buffer_rsrc((void *)jobs.j[ji].digest, 0, (int)jobs.j[ji].digest_bytes, 0x00020000);
     d.rs_phase = __builtin_amdgcn_make_buffer_rsrc((void *)jobs.j[ji].phase, 0, (int)((unsigned)W * (unsigned)H * 4u), 0x00020000);
     d.rs_valid = __builtin_amdgcn_make_buffer_rsrc((void *)jobs.j[ji].valid, 0, HASVALID ? (int)((unsigned)W * (unsigned)H) : 0, 0x00020000);
     d.sc.boxes = jobs.j[ji].boxes;
-    d.sc.ctr = sched + (ji * 8 + xcd) * kSchedStride;
+    d.sc.ctr = sched + (vi * 8 + xcd) * kSchedStride;
     d.sc.nxt = 0; d.sc.has_next = false; d.sc.voff_next = kDmaInvalid; d.sc.nxt_ty = d.sc.nxt_tx = 0; d.sc.nxt_act = false;
 #if defined(SLR_DMA_CLOCKPROBE)
     int it = 0;
@@ -1146,14 +1209,18 @@ void mf_rect_decode_dma_kernel(DmaJobs jobs, int njobs, int pitch, int W, int H,
     for (int a = 0; a < A; a++) d.issue_planes(a, a % Dec::D, voff_cur);
 
     for (;;) {
-        // the phase-0 buffer index advances by 7 mod D from tile to tile: D tiles per round of this loop
+        // the phase-0 buffer index advances by 7 mod D from unit to unit: D units per round of this loop
 #define SLR_DMA_TILE(K0)                                                                                       \
         {                                                                                                      \
             d.template tile<K0>(cur_ty, cur_tx, cur_act, voff_cur);                                            \
             SLR_DMA_COUNT(it);                                                                                 \
-            if (!d.sc.has_next) break;                                                                         \
-            cur = d.sc.nxt; voff_cur = d.sc.voff_next;                                                         \
-            cur_ty = d.sc.nxt_ty; cur_tx = d.sc.nxt_tx; cur_act = d.sc.nxt_act;                                \
+            if (!d.last_frame()) d.fk++;           /* the next frame of the visit: same entry */              \
+            else {                                                                                             \
+                d.fk = 0;                                                                                      \
+                if (!d.sc.has_next) break;                                                                     \
+                cur = d.sc.nxt; voff_cur = d.sc.voff_next;                                                     \
+                cur_ty = d.sc.nxt_ty; cur_tx = d.sc.nxt_tx; cur_act = d.sc.nxt_act;                            \
+            }                                                                                                  \
         }
         SLR_DMA_TILE(0)
         SLR_DMA_TILE(7 % Dec::D)
@@ -1283,8 +1350,11 @@ static bool dma_job(const MfPlanes &pl, int pitch, int W, int H, float *phase, u
 
 template <int TW, int TH, int NT, int A, bool HV, bool X87 = false>
 static hipError_t launch_dma_variant(const DmaJobs &j, int njobs, int pitch, int W, int H, int black_thr, const float *lut, unsigned *sched,
-                                     hipStream_t s)
+                                     hipStream_t s, int nsets)
 {
+    // nsets > 0: the njobs = 2 g frame jobs of a group run as 2 nsets visit jobs (see VISITS)
+    const int nframes = njobs / 2;
+    if (nsets > 0) njobs = 2 * nsets;
     typedef DmaDecode<TW, TH, NT, A, HV, X87> Dec;
     auto kern = mf_rect_decode_dma_kernel<TW, TH, NT, A, HV, X87>;
     static DevSlots resident;                             // resident workgroups of this kernel, per device
@@ -1311,7 +1381,7 @@ static hipError_t launch_dma_variant(const DmaJobs &j, int njobs, int pitch, int
     hipError_t e = hipMemsetAsync(sched, 0, kSchedBytes, s);
     if (e != hipSuccess) return e;
     SLR_LAUNCH(kern, dim3(8u * (unsigned)nbx * (unsigned)njobs), dim3(NT), Dec::LDS_BYTES, s, j, njobs, pitch, W, H, black_thr, lut,
-               tiles_x, tiles_y, sched);
+               tiles_x, tiles_y, sched, nsets, nframes);
     return hipGetLastError();
 }
 
@@ -1320,9 +1390,10 @@ static hipError_t launch_dma_variant(const DmaJobs &j, int njobs, int pitch, int
 // (stack layout, image width), nothing was launched.  depth: DMA issue distance A (1 or 2).
 hipError_t launch_mf_rect_decode_dma(const MfPlanes *pl, int n, int pitch, int W, int H, int black_thr, const float *lut,
                                      float *const *phase, uint8_t *const *valid, const void *const *tiles, int shape, int depth,
-                                     unsigned *sched, const DmaFixup *fix, bool *done, hipStream_t s, const int *fix_slot)
+                                     unsigned *sched, const DmaFixup *fix, bool *done, hipStream_t s, const int *fix_slot, int visit_frames)
 {
-    // fix_slot (n > 2: the cameras of a group of frames, job 2 f + cam): job c's slot in *fix; null: slot c
+    // fix_slot (n > 2: the cameras of a group of frames, job 2 f + cam): job c's slot in *fix; null: slot c.  visit_frames: frames per
+    // visit wanted for such a group (see VISITS)
     *done = false;
     if (shape < 0 || shape >= kDmaShapes || !sched || n < 1 || n > kDmaMaxJobs) return hipSuccess;
     auto slot = [&](int c) { return fix_slot ? fix_slot[c] : c; };
@@ -1336,18 +1407,31 @@ hipError_t launch_mf_rect_decode_dma(const MfPlanes *pl, int n, int pitch, int W
     for (int c = n; c < kDmaMaxJobs; c++) j.j[c] = j.j[0];
     const bool hv = valid[0] != nullptr;
     for (int c = 1; c < n; c++) if ((valid[c] != nullptr) != hv) return hipSuccess;
+    // Visits of several frames need the frames of a camera to differ in their stack and phase image only (one plane layout, one
+    // set of tile tables); the separate valid bytes of the single-frame entries stay at one frame per visit
+    int nsets = 0;
+    if (n > 2 && n % 2 == 0 && visit_frames > 1 && !hv) {
+        bool same = true;
+        for (int c = 2; c < n; c++) {
+            const DmaJob &a = j.j[c], &b = j.j[c & 1];
+            same = same && a.pstride == b.pstride && a.fringe_skip == b.fringe_skip && a.stack_bytes == b.stack_bytes && a.boxes == b.boxes &&
+                   a.digest == b.digest && a.digest_bytes == b.digest_bytes && a.entries == b.entries;
+        }
+        const int g = n / 2, f = visit_frames < kDmaMaxVisit ? visit_frames : kDmaMaxVisit;
+        if (same) nsets = (g + f - 1) / f;
+    }
     *done = true;
     hipError_t e = hipSuccess;
     // SLR_OPT_EVAL_MODEL = 1: the same kernel with the x87 heterodyne tail (`lut` is then the x87 variant of the tables); it exists at
     // the default DMA distance only (SLR_OPT_RECT_DMA_DEPTH is a tuning knob of the strict build)
     const bool x87 = tl_debug.eval_x87;
 #define SLR_DMA_X(TW, TH, NT)                                                                                          \
-    e = x87        ? (hv ? launch_dma_variant<TW, TH, NT, SLR_DMA_DEPTH2(TW, TH, NT), true, true>(j, n, pitch, W, H, black_thr, lut, sched, s)     \
-                         : launch_dma_variant<TW, TH, NT, SLR_DMA_DEPTH2(TW, TH, NT), false, true>(j, n, pitch, W, H, black_thr, lut, sched, s))   \
-      : depth >= 2 ? (hv ? launch_dma_variant<TW, TH, NT, SLR_DMA_DEPTH2(TW, TH, NT), true>(j, n, pitch, W, H, black_thr, lut, sched, s)     \
-                         : launch_dma_variant<TW, TH, NT, SLR_DMA_DEPTH2(TW, TH, NT), false>(j, n, pitch, W, H, black_thr, lut, sched, s))   \
-                   : (hv ? launch_dma_variant<TW, TH, NT, 1, true>(j, n, pitch, W, H, black_thr, lut, sched, s)              \
-                         : launch_dma_variant<TW, TH, NT, 1, false>(j, n, pitch, W, H, black_thr, lut, sched, s))
+    e = x87        ? (hv ? launch_dma_variant<TW, TH, NT, SLR_DMA_DEPTH2(TW, TH, NT), true, true>(j, n, pitch, W, H, black_thr, lut, sched, s, nsets)     \
+                         : launch_dma_variant<TW, TH, NT, SLR_DMA_DEPTH2(TW, TH, NT), false, true>(j, n, pitch, W, H, black_thr, lut, sched, s, nsets))   \
+      : depth >= 2 ? (hv ? launch_dma_variant<TW, TH, NT, SLR_DMA_DEPTH2(TW, TH, NT), true>(j, n, pitch, W, H, black_thr, lut, sched, s, nsets)     \
+                         : launch_dma_variant<TW, TH, NT, SLR_DMA_DEPTH2(TW, TH, NT), false>(j, n, pitch, W, H, black_thr, lut, sched, s, nsets))   \
+                   : (hv ? launch_dma_variant<TW, TH, NT, 1, true>(j, n, pitch, W, H, black_thr, lut, sched, s, nsets)              \
+                         : launch_dma_variant<TW, TH, NT, 1, false>(j, n, pitch, W, H, black_thr, lut, sched, s, nsets))
     SLR_DMA_SHAPE_SWITCH(shape, SLR_DMA_X)
 #undef SLR_DMA_X
     // the tiles this form does not hold (none for mild maps): rewritten behind the main kernel

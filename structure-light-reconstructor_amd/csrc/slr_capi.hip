@@ -1134,9 +1134,10 @@ static int decode_pair_dev(slr_ctx *c, const uint8_t *const *pL, const uint8_t *
     return SLR_OK;
 }
 
-// the fused decode of both cameras of g frames of a batch in ONE launch (LDS-DMA form only): job 2 f + cam; the workgroups of the
-// frames walk a camera's tiles at the same pace, so its map digest and boxes (4 of the decode's 23 bytes per camera pixel) cross HBM
-// once per group.  *grouped = false: nothing launched (the caller decodes frame by frame).  Phases of frame f at phL / phR + f * n.
+// the fused decode of both cameras of g frames of a batch in ONE launch (LDS-DMA form only): job 2 f + cam.  A workgroup decodes each
+// tile it draws for all frames of its camera (up to kDmaVisitFrames) back to back, so the tile's digest fetch, tap setup and ticket are
+// paid once per group (kernels_rectdma.hip, VISITS; SLR_OPT_DEBUG_FLAGS bit 10: one frame per visit, the frames' workgroups walking the
+// camera's tiles side by side).  *grouped = false: nothing launched (the caller decodes frame by frame).  Phases of frame f at phL / phR + f * n.
 static int decode_group_dev(slr_ctx *c, int g, const uint8_t *stack, size_t plane, int pitch, int W, int H, int black_thr,
                             float *phL, float *phR, bool *grouped, const MfPlanes *sets = nullptr /* [2 g]: job 2 f + cam (else: from `stack`) */)
 {
@@ -1164,7 +1165,7 @@ static int decode_group_dev(slr_ctx *c, int g, const uint8_t *stack, size_t plan
     ProfScope ps(c, K_MF_RECT_DECODE_PAIR, true);
     ps.r.units = g;
     SLR_HIP(c, launch_mf_rect_decode_dma(mp, 2 * g, pitch, W, H, black_thr, c->d_lut, ph, vd, tl, c->opt_dma_shape, c->opt_dma_depth,
-                                         c->d_sched, &fix, grouped, c->stream, slot));
+                                         c->d_sched, &fix, grouped, c->stream, slot, c->debug.one_frame_visits ? 1 : kDmaVisitFrames));
     return SLR_OK;
 }
 
@@ -2178,8 +2179,9 @@ int slr_set_option(slr_ctx *c, int option, int value)
             c->debug.rect_resident = value;
             return SLR_OK;
         case SLR_OPT_DEBUG_FLAGS:
-            if (value < 0 || value > 1023) return fail(c, SLR_ERR_INVALID_ARG, "SLR_OPT_DEBUG_FLAGS must be 0..1023");
+            if (value < 0 || value > 2047) return fail(c, SLR_ERR_INVALID_ARG, "SLR_OPT_DEBUG_FLAGS must be 0..2047");
             c->debug.fuse_count_atomics = (value & 512) != 0;
+            c->debug.one_frame_visits = (value & 1024) != 0;
             c->debug.mfn_nt512 = (value & 128) != 0;
             c->debug.mfn_ring4 = (value & 256) != 0;
             c->debug.no_tiled_map = (value & 1) != 0;

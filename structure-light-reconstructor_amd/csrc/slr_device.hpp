@@ -76,6 +76,7 @@ struct DebugKnobs {
     int k4_stop = 0;
     bool poison_scratch = false; // SLR_OPT_DEBUG_POISON_SCRATCH
     bool fuse_count_atomics = false; // slr_fuse_voxels: count the insert pass's atomics (slr_fuse_last_stats)
+    bool one_frame_visits = false;   // grouped LDS-DMA fused decode: one frame per visit of a tile (else kDmaVisitFrames)
     bool eval_x87 = false;       // SLR_OPT_EVAL_MODEL = 1 (not a debug knob, but it travels the same way: per call, per thread)
 };
 extern thread_local DebugKnobs tl_debug;
@@ -147,8 +148,10 @@ struct DmaFixup {
 hipError_t launch_mf_rect_decode_dma(const MfPlanes *pl, int n, int pitch, int W, int H, int black_thr, const float *lut,
                                      float *const *phase, uint8_t *const *valid, const void *const *tiles, int shape, int depth,
                                      unsigned *sched /* dma_sched_bytes() of zeros, owned by the context: the tile tickets */,
-                                     const DmaFixup *fix, bool *done, hipStream_t s, const int *fix_slot = nullptr);
+                                     const DmaFixup *fix, bool *done, hipStream_t s, const int *fix_slot = nullptr,
+                                     int visit_frames = 1 /* n > 2: frames of a group decoded back to back per tile (kernels_rectdma.hip, VISITS) */);
 constexpr int kDmaMaxJobs = 16;  // (frame, camera) jobs of one fused-decode launch: the two cameras of up to 8 frames
+constexpr int kDmaVisitFrames = 8;   // frames per visit of the grouped fused decode (SLR_OPT_DEBUG_FLAGS bit 10: 1)
 size_t     dma_sched_bytes();
 
 hipError_t launch_gray_rect_decode_dma(const GrayPlanes *pl, int n, int ncol, int nrow, int pitch, int W, int H, int black_thr,

@@ -517,6 +517,66 @@ int slr_fuse_voxels(slr_ctx *ctx, const slr_fuse_desc *desc, const float *xyz, c
                     uint64_t *n_rejected, slr_mem mem);
 int slr_fuse_last_stats(slr_ctx *ctx, slr_fuse_stats *out);
 
+/* ---- rigid registration: point-to-plane ICP with projective association ----------------------------------------------------
+ * What slr_fuse_voxels needs and the reference gets from marker dots (DotMatch, out of scope): the 3x4 T that maps a SOURCE point set
+ * into the frame of a TARGET cloud organised on its camera grid -- the convention of transfer_mat and of slr_fuse_voxels' T.
+ * A source point finds its target by projecting into the target's pinhole grid (no search structure).
+ *   target: dst_xyz [H][W][3] f32, dst_has [H][W] u8 (non-zero = point), the grid of a pinhole (fx, fy, cx, cy) whose camera sits at
+ *           the origin looking along +z.  For a K4 cloud (slr_reconstruct_mf*, no calibration T): fx = fy = Q[2][3], cx = -Q[0][3],
+ *           cy = -Q[1][3] (capi.pinhole_from_Q).
+ *   source: src_xyz [n_src][3] f32 -- any point list (an organised grid flattened, or a fused cloud) -- and src_has [n_src] u8 or NULL
+ *           (every point present); n_src < 2^32.
+ * Normals (slr_cloud_normals; every step f64 and correctly rounded, in exactly this order; P = the f32 point widened):
+ *   pixel (i, j) has a normal iff 1 <= i < H-1, 1 <= j < W-1, has is set at (i, j), (i, j-1), (i, j+1), (i-1, j), (i+1, j), and each
+ *   of those four neighbours X satisfies ((d_x d_x + d_y d_y) + d_z d_z) <= max_edge max_edge, d = X - P(i, j);
+ *   a = P(i, j+1) - P(i, j-1),  b = P(i+1, j) - P(i-1, j),  n = (a_y b_z - a_z b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x),
+ *   m = sqrt((n_x n_x + n_y n_y) + n_z n_z);  m == 0: no normal;  n = n / m;  if ((n_x P_x + n_y P_y) + n_z P_z) > 0: n = -n;
+ *   normals[i][j] = (float)n, nvalid[i][j] = 1.  Without a normal: (0, 0, 0) and nvalid = 0.
+ * Linearisation (slr_icp_linearize; T is the current f64 3x4 estimate), per source point s with has != 0 and three finite coordinates:
+ *   q_r = ((T[r][0] s_0 + T[r][1] s_1) + T[r][2] s_2) + T[r][3];  rejected if q_z <= 0;
+ *   u = q_x / q_z fx + cx,  v = q_y / q_z fy + cy,  j = floor(u + 0.5),  i = floor(v + 0.5)  (range-checked as doubles: 0 <= j < W,
+ *   0 <= i < H);  the pixel needs dst_has and a normal;  d = q - P(i, j);  kept iff ((d_x d_x + d_y d_y) + d_z d_z) <= max_dist max_dist;
+ *   r = (n_x d_x + n_y d_y) + n_z d_z  (n widened),  J = (q x n, n) = (q_y n_z - q_z n_y, q_z n_x - q_x n_z, q_x n_y - q_y n_x, n_x, n_y, n_z).
+ *   sums[0..20] = the upper triangle of A = sum J J^T, row by row ((0,0), (0,1) .. (0,5), (1,1) .. (5,5)); sums[21..26] = b = sum J r;
+ *   sums[27] = e = sum r^2;  *inliers = the kept points (exact).  The f64 sums are formed in a fixed order for a given n_src (per
+ *   thread, a wave butterfly, the workgroup's waves, then the workgroups in ascending order; no floating-point atomics): the same inputs
+ *   give the same bits on every run.
+ * Registration (slr_register_icp): normals of the target into context scratch, then T = T_init (NULL: identity; used as given, not
+ * re-orthonormalised) and for it = 1 .. max_iters:
+ *   linearise at T;  res->inliers, res->rms = sqrt(e / inliers) (0 without inliers);
+ *   inliers < min_inliers: stop_reason 3;
+ *   solve A xi = -b by f64 Cholesky, xi = (omega, v).  A is taken as singular (stop_reason 4) when a pivot d_k (the k-th diagonal entry of
+ *   the factor, squared) is not > 1e-6 max(A_00, A_11, A_22) for k < 3, or not > 1e-6 max(A_33, A_44, A_55) for k >= 3 (a planar scene
+ *   leaves a rotation and two translations unconstrained: with the ~1e-4 normal noise of f32 coordinates its free directions show
+ *   pivots of ~1e-8 of their block, constrained ones 1e-3 and more.  Badly conditioned systems above the bound are solved; whether a
+ *   result is good enough is the caller's test, e.g. slr_icp_linearize at the start and at the result);
+ *   T = [R(omega) | v] T  with R(omega) = I + (sin t / t) [omega]x + (2 sin^2(t/2) / t^2) [omega]x^2, t = |omega| (I for t = 0);
+ *   res->iterations = it;  |omega| < stop_rot and |v| < stop_trans: stop_reason 1;  it == max_iters: stop_reason 2.
+ * On stop reasons 3 and 4 the call still returns SLR_OK with the last estimate (T_init when no update was made).  res->T = the f64
+ * estimate, T_out[12] = (float)res->T.  T, T_init, T_out, sums, inliers and res are ALWAYS host arrays; the point arrays follow `mem`
+ * (slr_cloud_normals' outputs too).  slr_icp_linearize and slr_register_icp are synchronous.  Argument errors return SLR_ERR_INVALID_ARG
+ * with nothing enqueued.  Scratch (kept by the context): normals 13 B per target pixel, 232 B per linearisation workgroup (at most 256). */
+typedef struct slr_icp_desc {
+    int W, H;                      /* target grid, W H < 2^31 */
+    double fx, fy, cx, cy;         /* target grid's pinhole (finite, fx and fy > 0) */
+    double max_dist;               /* association gate, cloud units (> 0, finite) */
+    double max_edge;               /* normals: neighbour distance bound (> 0, finite) */
+    int max_iters;                 /* 1..100 */
+    double stop_rot, stop_trans;   /* converged when |omega| < stop_rot (rad) and |v| < stop_trans (>= 0, finite) */
+    uint32_t min_inliers;          /* >= 6 */
+} slr_icp_desc;
+typedef struct slr_icp_result {
+    int iterations, stop_reason;   /* 1 converged, 2 max_iters, 3 too few inliers, 4 singular system */
+    uint64_t inliers; double rms;  /* of the last linearisation */
+    double T[12];                  /* the f64 estimate */
+} slr_icp_result;
+int slr_cloud_normals(slr_ctx *ctx, const float *xyz, const uint8_t *has, int W, int H, double max_edge, float *normals,
+                      uint8_t *nvalid, slr_mem mem);
+int slr_icp_linearize(slr_ctx *ctx, const slr_icp_desc *desc, const float *src_xyz, const uint8_t *src_has, size_t n_src,
+                      const float *dst_xyz, const uint8_t *dst_has, const double *T, double *sums, uint64_t *inliers, slr_mem mem);
+int slr_register_icp(slr_ctx *ctx, const slr_icp_desc *desc, const float *src_xyz, const uint8_t *src_has, size_t n_src,
+                     const float *dst_xyz, const uint8_t *dst_has, const float *T_init, float *T_out, slr_icp_result *res, slr_mem mem);
+
 /* page-locked host memory (the H2D / D2H copies of SLR_MEM_HOST calls are truly asynchronous only from / to it) */
 int slr_host_alloc(void **ptr, size_t bytes);
 int slr_host_free(void *ptr);

@@ -9,6 +9,8 @@ and the frame-sharding helper for multi-GPU runs (dist).  The directory name con
 (tests/conftest.py and bench.py do exactly that).  There is NO CPU fallback anywhere in this package.
 """
 from . import capi  # noqa: F401
-from .capi import Context, FuseDesc, FuseStats, SlrError, fuse_voxels, make_calib, make_camera  # noqa: F401
+from .capi import (Context, FuseDesc, FuseStats, IcpDesc, IcpResult, SlrError, fuse_voxels, make_calib, make_camera,  # noqa: F401
+                   pinhole_from_Q)
 
-__all__ = ["capi", "Context", "SlrError", "make_calib", "make_camera", "fuse_voxels", "FuseDesc", "FuseStats"]
+__all__ = ["capi", "Context", "SlrError", "make_calib", "make_camera", "fuse_voxels", "FuseDesc", "FuseStats",
+           "IcpDesc", "IcpResult", "pinhole_from_Q"]

@@ -48,6 +48,7 @@ SYMBOLS = [
     "slr_reconstruct_mf", "slr_reconstruct_ge", "slr_reconstruct_gray", "slr_reconstruct_mf_batch", "slr_reconstruct_batch", "slr_reconstruct_mf_cloud", "slr_reconstruct_mf_multi", "slr_reconstruct_mf_allgather", "slr_reconstruct_mf_allgather_ex", "slr_allgather_clouds", "slr_hybrid_rectify_decode_pair", "slr_reconstruct_hybrid_batch",
     "slr_prefix_index", "slr_compact_points", "slr_cloud_checksums", "slr_verify_assembled",
     "slr_fuse_voxels", "slr_fuse_last_stats",
+    "slr_cloud_normals", "slr_icp_linearize", "slr_register_icp",
     "slr_host_alloc", "slr_host_free",
     "slr_timer_begin", "slr_timer_end", "slr_stream_copy", "slr_stream_mix", "slr_profile_enable", "slr_profile_reset",
     "slr_profile_kernel_count", "slr_profile_kernel_name", "slr_profile_get",
@@ -83,6 +84,26 @@ class FuseDesc(C.Structure):
 
 class FuseStats(C.Structure):
     _fields_ = [("points", C.c_uint64), ("distinct", C.c_uint64), ("table_entries", C.c_uint64), ("atomics", C.c_uint64)]
+
+
+class IcpDesc(C.Structure):
+    _fields_ = [("W", C.c_int), ("H", C.c_int), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("max_dist", C.c_double), ("max_edge", C.c_double), ("max_iters", C.c_int), ("stop_rot", C.c_double),
+                ("stop_trans", C.c_double), ("min_inliers", C.c_uint32)]
+
+
+class IcpResult(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("stop_reason", C.c_int), ("inliers", C.c_uint64), ("rms", C.c_double), ("T", C.c_double * 12)]
+
+
+ICP_CONVERGED, ICP_MAX_ITERS, ICP_FEW_INLIERS, ICP_SINGULAR = 1, 2, 3, 4   # slr_icp_result.stop_reason
+
+
+def pinhole_from_Q(Q):
+    """(fx, fy, cx, cy) of the rectified left camera grid a K4 cloud lies on, from cv::stereoRectify's Q (4x4):
+    fx = fy = Q[2][3], cx = -Q[0][3], cy = -Q[1][3] -- the pinhole slr_register_icp projects into"""
+    Q = np.asarray(Q, np.float64).reshape(4, 4)
+    return float(Q[2, 3]), float(Q[2, 3]), float(-Q[0, 3]), float(-Q[1, 3])
 
 
 DEBUG_FUSE_COUNT_ATOMICS = 512  # SLR_OPT_DEBUG_FLAGS bit 9: slr_fuse_voxels counts its insert pass's atomics (fuse_last_stats)
@@ -728,6 +749,70 @@ class Context:
         s = FuseStats()
         self._chk(self.lib.slr_fuse_last_stats(self.h, C.byref(s)))
         return {"points": s.points, "distinct": s.distinct, "table_entries": s.table_entries, "atomics": s.atomics}
+
+    # -- registration (point-to-plane ICP; include/slr.h has the exact rule)
+    def cloud_normals(self, xyz, has, max_edge):
+        """slr_cloud_normals: xyz [H][W][3], has [H][W] (numpy or torch.cuda) -> (normals [H][W][3] f32, nvalid [H][W] u8)"""
+        if has.ndim != 2 or tuple(xyz.shape) != tuple(has.shape) + (3,):
+            raise ValueError("xyz must be [H][W][3] and has [H][W]")
+        H, W = has.shape
+        mem = self._mem([xyz, has])
+        nrm = self._new(mem, (H, W, 3), np.float32, xyz)
+        nv = self._new(mem, (H, W), np.uint8, xyz)
+        self._chk(self.lib.slr_cloud_normals(self.h, _ptr(xyz), _ptr(has), C.c_int(W), C.c_int(H), C.c_double(max_edge), _ptr(nrm),
+                                             _ptr(nv), C.c_int(mem)))
+        return nrm, nv
+
+    @staticmethod
+    def _icp_args(src_xyz, src_has, dst_xyz, dst_has):
+        if dst_has.ndim != 2 or tuple(dst_xyz.shape) != tuple(dst_has.shape) + (3,):
+            raise ValueError("dst_xyz must be [H][W][3] and dst_has [H][W]")
+        if src_xyz.shape[-1] != 3:
+            raise ValueError("src_xyz must be [..][3]")
+        n = int(np.prod(tuple(src_xyz.shape[:-1])))
+        if src_has is not None and int(np.prod(tuple(src_has.shape))) != n:
+            raise ValueError("src_has must hold one byte per source point")
+        return n, dst_has.shape[1], dst_has.shape[0]
+
+    @staticmethod
+    def _icp_desc(W, H, pinhole, max_dist, max_edge, max_iters=1, stop_rot=0.0, stop_trans=0.0, min_inliers=6):
+        fx, fy, cx, cy = (float(v) for v in pinhole)
+        return IcpDesc(int(W), int(H), fx, fy, cx, cy, float(max_dist), float(max_edge), int(max_iters), float(stop_rot),
+                       float(stop_trans), int(min_inliers))
+
+    def icp_linearize(self, src_xyz, src_has, dst_xyz, dst_has, pinhole, T, max_dist, max_edge):
+        """slr_icp_linearize: one point-to-plane linearisation of the source [..][3] (src_has or None) against the organised target
+        [H][W][3] / [H][W] at the 3x4 estimate T (f64) -> (sums [28] f64: 21 upper A, 6 b, e; inlier count)"""
+        n, W, H = self._icp_args(src_xyz, src_has, dst_xyz, dst_has)
+        mem = self._mem([src_xyz, src_has, dst_xyz, dst_has])
+        Th = np.ascontiguousarray(np.asarray(T, np.float64).reshape(12))
+        desc = self._icp_desc(W, H, pinhole, max_dist, max_edge)
+        sums, inl = np.zeros(28, np.float64), C.c_uint64(0)
+        self._chk(self.lib.slr_icp_linearize(self.h, C.byref(desc), _ptr(src_xyz), _ptr(src_has), C.c_size_t(n), _ptr(dst_xyz),
+                                             _ptr(dst_has), _ptr(Th), _ptr(sums), C.byref(inl), C.c_int(mem)))
+        return sums, inl.value
+
+    def register_icp(self, src_xyz, src_has, dst_xyz, dst_has, pinhole, T_init=None, max_dist=20.0, max_edge=10.0, max_iters=30,
+                     stop_rot=1e-6, stop_trans=1e-4, min_inliers=6):
+        """slr_register_icp: the 3x4 T mapping the source points [..][3] (src_has or None) into the frame of the target organised
+        on the pinhole grid `pinhole` = (fx, fy, cx, cy) (pinhole_from_Q for K4 clouds).  Numpy arrays (host) or torch.cuda tensors
+        (device); T_init: None (identity) or a 3x4 / 12 (numpy or torch).  -> (T [3][4] f32 numpy, dict of the result fields with
+        T64 the f64 estimate)"""
+        n, W, H = self._icp_args(src_xyz, src_has, dst_xyz, dst_has)
+        mem = self._mem([src_xyz, src_has, dst_xyz, dst_has])
+        Ti = None
+        if T_init is not None:
+            Tn = T_init.detach().cpu().numpy() if _is_torch(T_init) else np.asarray(T_init)
+            if Tn.size != 12:
+                raise ValueError("T_init must be a 3x4 transform")
+            Ti = np.ascontiguousarray(Tn, dtype=np.float32).reshape(12)
+        desc = self._icp_desc(W, H, pinhole, max_dist, max_edge, max_iters, stop_rot, stop_trans, min_inliers)
+        T = np.zeros(12, np.float32)
+        res = IcpResult()
+        self._chk(self.lib.slr_register_icp(self.h, C.byref(desc), _ptr(src_xyz), _ptr(src_has), C.c_size_t(n), _ptr(dst_xyz),
+                                            _ptr(dst_has), _ptr(Ti), _ptr(T), C.byref(res), C.c_int(mem)))
+        return T.reshape(3, 4), {"iterations": res.iterations, "stop_reason": res.stop_reason, "inliers": res.inliers, "rms": res.rms,
+                                 "T64": np.array(list(res.T), np.float64).reshape(3, 4)}
 
     # -- measurement
     def cloud_checksums(self, xyz, has):

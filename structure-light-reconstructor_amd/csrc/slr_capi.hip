@@ -24,7 +24,8 @@ const char *kKernelNames[K_COUNT] = {
     "slr_ray_triangulate",
     "slr_pc_from_grid", "slr_pc_get", "slr_undistort_table", "slr_ray_table", "slr_mf_rectify_decode_pair", "slr_mfn_decode",
     "slr_gray_rectify_decode_pair", "slr_hybrid_rectify_decode_pair", "slr_mfn_rectify_decode",
-    "slr_fuse_clear", "slr_fuse_insert", "slr_fuse_total", "slr_fuse_flag", "slr_fuse_scan", "slr_fuse_emit"};
+    "slr_fuse_clear", "slr_fuse_insert", "slr_fuse_total", "slr_fuse_flag", "slr_fuse_scan", "slr_fuse_emit",
+    "slr_icp_normals", "slr_icp_linearize", "slr_icp_reduce"};
 
 // scratch slots (device buffers owned by the ctx, grown on demand, reused across calls)
 enum Slot {
@@ -34,6 +35,7 @@ enum Slot {
     S_RAY_CELL, S_RAY_CELL2, S_RAY_RANK, S_RAY_CNT, S_RAY_OFFS, S_RAY_ITEMS, S_RAY_LIST, S_SCAN_TMP,
     S_XYZ, S_HAS, S_COLOR, S_UND_L, S_UND_R, S_RAYS_L, S_RAYS_R, S_FLAGSCAN, S_COMPACT, S_K4_DEFER,
     S_FUSE_TABLE, S_FUSE_STATS, S_FUSE_FLAGS, S_FUSE_SRC, S_FUSE_T,
+    S_ICP_NORMALS, S_ICP_NVALID, S_ICP_PARTIALS, S_ICP_SUMS,
     S_COUNT
 };
 
@@ -1713,6 +1715,206 @@ int slr_fuse_last_stats(slr_ctx *c, slr_fuse_stats *out)
 {
     if (!c || !out) return fail(c, SLR_ERR_INVALID_ARG, "null argument");
     *out = c->fuse_stats;
+    return SLR_OK;
+}
+
+// ---- point-to-plane ICP (kernels_icp.hip) ----------------------------------------------------------------------------------------
+namespace {
+
+int icp_check_grid(slr_ctx *c, int W, int H)
+{
+    if (W < 1 || H < 1 || (long long)W * H >= (1ll << 31)) return fail(c, SLR_ERR_INVALID_ARG, "target W and H must be >= 1, W * H < 2^31");
+    return SLR_OK;
+}
+
+int icp_check_desc(slr_ctx *c, const slr_icp_desc *d)
+{
+    SLR_TRY(icp_check_grid(c, d->W, d->H));
+    if (!isfinite(d->fx) || !isfinite(d->fy) || !(d->fx > 0) || !(d->fy > 0) || !isfinite(d->cx) || !isfinite(d->cy))
+        return fail(c, SLR_ERR_INVALID_ARG, "fx, fy must be finite and > 0, cx, cy finite");
+    if (!isfinite(d->max_dist) || !(d->max_dist > 0)) return fail(c, SLR_ERR_INVALID_ARG, "max_dist must be finite and > 0");
+    if (!isfinite(d->max_edge) || !(d->max_edge > 0)) return fail(c, SLR_ERR_INVALID_ARG, "max_edge must be finite and > 0");
+    if (d->max_iters < 1 || d->max_iters > 100) return fail(c, SLR_ERR_INVALID_ARG, "max_iters must be 1..100");
+    if (!isfinite(d->stop_rot) || !(d->stop_rot >= 0) || !isfinite(d->stop_trans) || !(d->stop_trans >= 0))
+        return fail(c, SLR_ERR_INVALID_ARG, "stop_rot and stop_trans must be finite and >= 0");
+    if (d->min_inliers < 6) return fail(c, SLR_ERR_INVALID_ARG, "min_inliers must be >= 6");
+    return SLR_OK;
+}
+
+// one linearisation at T (the normals already in L.normals / L.nvalid): sums[28] and the inlier count, synchronously
+int icp_linearize_at(slr_ctx *c, IcpLaunch &L, double *sums_dev, const double T[12], double sums[28], uint64_t *inliers)
+{
+    for (int k = 0; k < 12; k++) L.T[k] = T[k];
+    { ProfScope ps(c, K_ICP_LINEARIZE, true); SLR_HIP(c, launch_icp_linearize(L, c->stream)); }
+    { ProfScope ps(c, K_ICP_REDUCE, true); SLR_HIP(c, launch_icp_reduce(L.partials, L.groups, sums_dev, c->stream)); }
+    double out[kIcpSums];
+    SLR_HIP(c, hipMemcpyAsync(out, sums_dev, sizeof out, hipMemcpyDeviceToHost, c->stream));
+    SLR_HIP(c, hipStreamSynchronize(c->stream));
+    memcpy(sums, out, 28 * sizeof(double));
+    memcpy(inliers, &out[28], sizeof(uint64_t));
+    return SLR_OK;
+}
+
+// the shared setup of slr_icp_linearize and slr_register_icp: staging, the target normals, the partials
+int icp_setup(slr_ctx *c, Stage &st, const slr_icp_desc *d, const float *src, const uint8_t *src_has, size_t n_src, const float *dst,
+              const uint8_t *dst_has, IcpLaunch *L, double **sums_dev)
+{
+    const size_t px = (size_t)d->W * d->H;
+    const void *ds, *dsh, *dd, *ddh;
+    SLR_TRY(st.in(src, n_src * 12, &ds)); SLR_TRY(st.in(src_has, n_src, &dsh));
+    SLR_TRY(st.in(dst, px * 12, &dd)); SLR_TRY(st.in(dst_has, px, &ddh));
+    void *nrm, *nval, *part, *sd;
+    SLR_TRY(get_scratch(c, S_ICP_NORMALS, px * 12, &nrm));
+    SLR_TRY(get_scratch(c, S_ICP_NVALID, px, &nval));
+    SLR_TRY(get_scratch(c, S_ICP_PARTIALS, icp_partial_bytes(n_src), &part));
+    SLR_TRY(get_scratch(c, S_ICP_SUMS, kIcpSums * sizeof(double), &sd));
+    *L = IcpLaunch{};
+    L->src = (const float *)ds; L->src_has = (const uint8_t *)dsh; L->n = n_src;
+    L->dst = (const float *)dd; L->dst_has = (const uint8_t *)ddh; L->normals = (const float *)nrm; L->nvalid = (const uint8_t *)nval;
+    L->W = d->W; L->H = d->H; L->fx = d->fx; L->fy = d->fy; L->cx = d->cx; L->cy = d->cy;
+    L->max_dist2 = d->max_dist * d->max_dist;
+    L->partials = (double *)part; L->groups = icp_groups(n_src);
+    *sums_dev = (double *)sd;
+    ProfScope ps(c, K_ICP_NORMALS, true);
+    SLR_HIP(c, launch_icp_normals(L->dst, L->dst_has, d->W, d->H, d->max_edge, (float *)nrm, (uint8_t *)nval, c->stream));
+    return SLR_OK;
+}
+
+// A xi = -b by Cholesky (A from the 21 upper sums, b from the next 6); false: A is singular in the sense of include/slr.h
+bool icp_solve(const double *sums, double xi[6])
+{
+    double A[6][6], L[6][6] = {};
+    int k = 0;
+    for (int r = 0; r < 6; r++)
+        for (int col = r; col < 6; col++) A[r][col] = A[col][r] = sums[k++];
+    const double rot = fmax(fmax(A[0][0], A[1][1]), A[2][2]), tra = fmax(fmax(A[3][3], A[4][4]), A[5][5]);
+    if (!(rot > 0) || !(tra > 0) || !isfinite(rot) || !isfinite(tra)) return false;
+    for (int j = 0; j < 6; j++) {
+        double dj = A[j][j];
+        for (int m = 0; m < j; m++) dj -= L[j][m] * L[j][m];
+        if (!(dj > 1e-6 * (j < 3 ? rot : tra))) return false;
+        L[j][j] = sqrt(dj);
+        for (int i = j + 1; i < 6; i++) {
+            double s = A[i][j];
+            for (int m = 0; m < j; m++) s -= L[i][m] * L[j][m];
+            L[i][j] = s / L[j][j];
+        }
+    }
+    double y[6];
+    for (int i = 0; i < 6; i++) {
+        double s = -sums[21 + i];
+        for (int m = 0; m < i; m++) s -= L[i][m] * y[m];
+        y[i] = s / L[i][i];
+    }
+    for (int i = 5; i >= 0; i--) {
+        double s = y[i];
+        for (int m = i + 1; m < 6; m++) s -= L[m][i] * xi[m];
+        xi[i] = s / L[i][i];
+    }
+    return true;
+}
+
+// T = [R(omega) | v] T
+void icp_update(const double xi[6], double T[12])
+{
+    const double w0 = xi[0], w1 = xi[1], w2 = xi[2];
+    const double t = sqrt((w0 * w0 + w1 * w1) + w2 * w2);
+    double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    if (t > 0) {
+        const double a = sin(t) / t, h = sin(0.5 * t), b = 2 * h * h / (t * t);
+        const double K[3][3] = {{0, -w2, w1}, {w2, 0, -w0}, {-w1, w0, 0}};
+        for (int r = 0; r < 3; r++)
+            for (int col = 0; col < 3; col++) {
+                double kk = 0;
+                for (int m = 0; m < 3; m++) kk += K[r][m] * K[m][col];
+                R[r][col] += a * K[r][col] + b * kk;
+            }
+    }
+    double out[12];
+    for (int r = 0; r < 3; r++)
+        for (int col = 0; col < 4; col++) {
+            double s = 0;
+            for (int m = 0; m < 3; m++) s += R[r][m] * T[4 * m + col];
+            out[4 * r + col] = col == 3 ? s + xi[3 + r] : s;
+        }
+    memcpy(T, out, sizeof out);
+}
+
+}  // namespace
+
+int slr_cloud_normals(slr_ctx *c, const float *xyz, const uint8_t *has, int W, int H, double max_edge, float *normals, uint8_t *nvalid,
+                      slr_mem mem)
+{
+    if (!c) return SLR_ERR_INVALID_ARG;
+    if (!xyz || !has || !normals || !nvalid) return fail(c, SLR_ERR_INVALID_ARG, "null argument");
+    if (mem != SLR_MEM_HOST && mem != SLR_MEM_DEVICE) return fail(c, SLR_ERR_INVALID_ARG, "bad memory kind");
+    SLR_TRY(icp_check_grid(c, W, H));
+    if (!isfinite(max_edge) || !(max_edge > 0)) return fail(c, SLR_ERR_INVALID_ARG, "max_edge must be finite and > 0");
+    SLR_TRY(use_device(c));
+    const size_t px = (size_t)W * H;
+    Stage st(c, mem);
+    const void *dx, *dh;
+    void *dn, *dv;
+    SLR_TRY(st.in(xyz, px * 12, &dx)); SLR_TRY(st.in(has, px, &dh));
+    SLR_TRY(st.out(normals, px * 12, &dn)); SLR_TRY(st.out(nvalid, px, &dv));
+    { ProfScope ps(c, K_ICP_NORMALS, true);
+      SLR_HIP(c, launch_icp_normals((const float *)dx, (const uint8_t *)dh, W, H, max_edge, (float *)dn, (uint8_t *)dv, c->stream)); }
+    return st.finish();
+}
+
+int slr_icp_linearize(slr_ctx *c, const slr_icp_desc *d, const float *src_xyz, const uint8_t *src_has, size_t n_src,
+                      const float *dst_xyz, const uint8_t *dst_has, const double *T, double *sums, uint64_t *inliers, slr_mem mem)
+{
+    if (!c) return SLR_ERR_INVALID_ARG;
+    if (!d || !src_xyz || !dst_xyz || !dst_has || !T || !sums || !inliers) return fail(c, SLR_ERR_INVALID_ARG, "null argument");
+    if (mem != SLR_MEM_HOST && mem != SLR_MEM_DEVICE) return fail(c, SLR_ERR_INVALID_ARG, "bad memory kind");
+    SLR_TRY(icp_check_desc(c, d));
+    if (n_src >= (1ull << 32)) return fail(c, SLR_ERR_INVALID_ARG, "n_src must be < 2^32");
+    for (int k = 0; k < 12; k++) if (!isfinite(T[k])) return fail(c, SLR_ERR_INVALID_ARG, "T must be finite");
+    SLR_TRY(use_device(c));
+    Stage st(c, mem);
+    IcpLaunch L;
+    double *sd;
+    SLR_TRY(icp_setup(c, st, d, src_xyz, src_has, n_src, dst_xyz, dst_has, &L, &sd));
+    return icp_linearize_at(c, L, sd, T, sums, inliers);
+}
+
+int slr_register_icp(slr_ctx *c, const slr_icp_desc *d, const float *src_xyz, const uint8_t *src_has, size_t n_src,
+                     const float *dst_xyz, const uint8_t *dst_has, const float *T_init, float *T_out, slr_icp_result *res, slr_mem mem)
+{
+    if (!c) return SLR_ERR_INVALID_ARG;
+    if (!d || !src_xyz || !dst_xyz || !dst_has || !T_out || !res) return fail(c, SLR_ERR_INVALID_ARG, "null argument");
+    if (mem != SLR_MEM_HOST && mem != SLR_MEM_DEVICE) return fail(c, SLR_ERR_INVALID_ARG, "bad memory kind");
+    SLR_TRY(icp_check_desc(c, d));
+    if (n_src >= (1ull << 32)) return fail(c, SLR_ERR_INVALID_ARG, "n_src must be < 2^32");
+    double T[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    if (T_init) {
+        for (int k = 0; k < 12; k++) T[k] = (double)T_init[k];
+        for (int k = 0; k < 12; k++) if (!isfinite(T[k])) return fail(c, SLR_ERR_INVALID_ARG, "T_init must be finite");
+    }
+    SLR_TRY(use_device(c));
+    Stage st(c, mem);
+    IcpLaunch L;
+    double *sd;
+    SLR_TRY(icp_setup(c, st, d, src_xyz, src_has, n_src, dst_xyz, dst_has, &L, &sd));
+    slr_icp_result r = {};
+    r.stop_reason = 2;
+    for (int it = 1; it <= d->max_iters; it++) {
+        double sums[28], xi[6];
+        uint64_t n_in = 0;
+        SLR_TRY(icp_linearize_at(c, L, sd, T, sums, &n_in));
+        r.inliers = n_in;
+        r.rms = n_in ? sqrt(sums[27] / (double)n_in) : 0.0;
+        if (n_in < d->min_inliers) { r.stop_reason = 3; break; }
+        if (!icp_solve(sums, xi)) { r.stop_reason = 4; break; }
+        icp_update(xi, T);
+        r.iterations = it;
+        const double wn = sqrt((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2]), vn = sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5]);
+        if (wn < d->stop_rot && vn < d->stop_trans) { r.stop_reason = 1; break; }
+    }
+    memcpy(r.T, T, sizeof T);
+    for (int k = 0; k < 12; k++) T_out[k] = (float)T[k];
+    *res = r;
     return SLR_OK;
 }
 

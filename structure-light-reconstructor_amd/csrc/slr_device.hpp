@@ -49,7 +49,8 @@ struct DevCalib {
 enum KernelId {
     K_REMAP = 0, K_MF_DECODE, K_MF_RECT_DECODE, K_GRAY_DECODE, K_GRAY_RECT_DECODE,
     K_MF_MATCH, K_GE_MATCH, K_RAY_COUNT, K_RAY_SCAN, K_RAY_SCATTER, K_RAY_TRI, K_PC_FROM_GRID, K_PC_GET, K_UNDISTORT_TABLE, K_RAY_TABLE, K_MF_RECT_DECODE_PAIR, K_MFN_DECODE, K_GRAY_RECT_DECODE_PAIR, K_HYBRID_RECT_DECODE_PAIR, K_MFN_RECT_DECODE,
-    K_FUSE_CLEAR, K_FUSE_INSERT, K_FUSE_TOTAL, K_FUSE_FLAG, K_FUSE_SCAN, K_FUSE_EMIT, K_COUNT
+    K_FUSE_CLEAR, K_FUSE_INSERT, K_FUSE_TOTAL, K_FUSE_FLAG, K_FUSE_SCAN, K_FUSE_EMIT,
+    K_ICP_NORMALS, K_ICP_LINEARIZE, K_ICP_REDUCE, K_COUNT
 };
 
 // Every kernel launch goes through SLR_LAUNCH.  When the C-ABI layer's profiler has armed a pair of events for the
@@ -256,6 +257,25 @@ size_t     fuse_table_entries(uint32_t max_voxels);
 size_t     fuse_table_bytes(uint32_t max_voxels);
 size_t     fuse_stats_bytes();
 hipError_t launch_fuse_voxels(const FuseLaunch &L, int phase, hipStream_t s);
+
+// point-to-plane ICP with projective association (kernels_icp.hip; slr_cloud_normals, slr_icp_linearize, slr_register_icp).
+// normals: [H][W][3] f32 + nvalid [H][W] u8 of an organised target.  linearize: icp_groups(n) workgroups, each writes its column of
+// partials ([kIcpSums][groups]: 28 f64 rows, then the inlier count as u64); reduce: one workgroup sums the rows into out[kIcpSums].
+constexpr int kIcpSums = 29;
+struct IcpLaunch {
+    const float *src; const uint8_t *src_has /* or null */; size_t n;
+    const float *dst; const uint8_t *dst_has; const float *normals; const uint8_t *nvalid;
+    int W, H;
+    double fx, fy, cx, cy, max_dist2;
+    double T[12];                          // the current estimate, row-major 3x4
+    double *partials; unsigned groups;
+};
+unsigned   icp_groups(size_t n_src);
+size_t     icp_partial_bytes(size_t n_src);
+hipError_t launch_icp_normals(const float *xyz, const uint8_t *has, int W, int H, double max_edge, float *normals, uint8_t *nvalid,
+                              hipStream_t s);
+hipError_t launch_icp_linearize(const IcpLaunch &L, hipStream_t s);
+hipError_t launch_icp_reduce(const double *partials, unsigned groups, double *out, hipStream_t s);
 
 hipError_t launch_pc_from_grid(const float *xyz, const uint8_t *has, const uint8_t *color, int W, int H,
                                int scan_w, int scan_h, float *pc_sum, uint8_t *pc_count, uint8_t *pc_color,

@@ -1,5 +1,6 @@
 // duke_c.cpp -- extern "C" hooks over the C++ host mirror (libslr_host.so) so tests can drive it through ctypes, and
 // the body of slr_cli.  duke_run_project mirrors MainWindow::startreconstruct (Duke/mainwindow.cpp:562-652).
+#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -382,6 +383,152 @@ int duke_fuse_series(const char *project, int sn_first, int n_scans, int scan_w,
         d.max_voxels = cap;
         uint64_t rejected = 0;
         const int st = slr_fuse_voxels(ctx, &d, pts.data(), has.data(), nullptr, nullptr, fused.data(), count.data(), nullptr, &m,
+                                       &rejected, SLR_MEM_HOST);
+        if (st == SLR_OK) break;
+        if (st == SLR_ERR_OOM && cap < n && cap < (1u << 30)) {
+            const size_t want = std::max<size_t>((size_t)cap * 2, m);
+            cap = (uint32_t)std::min<size_t>(std::min<size_t>(want, n), (size_t)1 << 30);
+            continue;
+        }
+        set_err(err, err_len, std::string("slr_fuse_voxels: ") + slr_last_error(ctx));
+        return 0;
+    }
+    if (out_xyz) memcpy(out_xyz, fused.data(), (size_t)m * 12);
+    if (n_voxels) *n_voxels = m;
+    if (!writePointsPly(fused_ply, fused.data(), m)) { set_err(err, err_len, std::string("cannot write ") + fused_ply); return 0; }
+    set_err(err, err_len, "");
+    return 1;
+    DUKE_GUARD_END(0, err, err_len)
+}
+
+// duke_fuse_series with the scans registered first: every scan after the first is registered against the first scan's cloud by
+// slr_register_icp (point-to-plane ICP from identity, association gate max_dist, normals' neighbour bound max_dist as well), and the
+// fusion applies each scan's correction as its per-frame T.  A correction is APPLIED only when the loop converged (stop_reason 1) and
+// the fit at the result is no worse than at identity: slr_icp_linearize with the same gate keeps at least as many points there, with
+// an rms no larger.  The loop has no robust weights and can drift on terraced K4 clouds from starts that are not close (DESIGN.md
+// section 11); a scan whose correction is not applied keeps its transfer_mat (identity correction in the fusion).
+// The scans' clouds have already been moved by their transfer_mat, so an applied correction refines it to correction o original,
+// written as <project>/reconstruction/transfer_mat<sn>.txt (exportMat, the reference's text format); for a scan whose correction is
+// not applied that file is removed.  The first scan is the anchor: sn_first must be 0 (scan 0 carries no transfer_mat).  The target
+// is the first scan's PointCloudImage transposed back onto the rectified left camera grid (pc[j][i] -> grid[i][j]: min(cam_h,
+// scan_w) rows x min(cam_w, scan_h) columns) with the pinhole of the project's Q (fx = fy = Q[2][3], cx = -Q[0][3], cy = -Q[1][3]).
+// T_refined [n_scans][12] (the transfer_mat each scan ends with, f32), results [n_scans] (the loops' results; scan 0: identity,
+// stop_reason 0) and applied [n_scans] (1 = the correction was applied; scan 0: 1) may be NULL; the rest as duke_fuse_series.
+// Returns 1 on success, 0 on failure (err says why).
+int duke_register_fuse_series(const char *project, int sn_first, int n_scans, int scan_w, int scan_h, int cam_w, int cam_h, int black_thr,
+                              int white_thr, const char *suffix, const char *ply_prefix, const int *devices, int n_devices, double voxel,
+                              unsigned min_points, const char *fused_ply, double max_dist, float *T_refined, slr_icp_result *results,
+                              int *applied, float *out_xyz, uint32_t *n_voxels, char *err, int err_len)
+{
+    DUKE_GUARD_BEGIN
+    if (!project || !fused_ply || n_scans < 1 || scan_w <= 0 || scan_h <= 0 || cam_w <= 0 || cam_h <= 0 || !(voxel > 0) || min_points < 1 ||
+        !(max_dist > 0) || !(max_dist < 1e300)) {
+        set_err(err, err_len, "bad argument");
+        return 0;
+    }
+    if (sn_first != 0) { set_err(err, err_len, "registration needs the series to start at scan 0 (the anchor, no transfer_mat)"); return 0; }
+    const size_t cells = (size_t)scan_w * scan_h, n = cells * (size_t)n_scans;
+    if (n >= (1ull << 32)) { set_err(err, err_len, "n_scans * scan_w * scan_h must be < 2^32"); return 0; }
+    stereoRect sr(project, cam_w, cam_h);
+    sr.getParameters();
+    sr.calRectification();
+    if (sr.Q.empty()) { set_err(err, err_len, "stereo calibration files missing"); return 0; }
+    std::vector<float> pc_sum(n * 3), pts(n * 3);
+    std::vector<uint8_t> pc_count(n), has(n);
+    const int done = n_devices > 0
+        ? duke_run_series_multi(project, sn_first, n_scans, scan_w, scan_h, cam_w, cam_h, black_thr, white_thr, suffix, ply_prefix, devices,
+                                n_devices, pc_sum.data(), pc_count.data(), err, err_len)
+        : duke_run_series(project, sn_first, n_scans, scan_w, scan_h, cam_w, cam_h, black_thr, white_thr, suffix, ply_prefix, pc_sum.data(),
+                          pc_count.data(), err, err_len);
+    if (done != n_scans) return 0;
+    int dev = 0;
+    slr_ctx *ctx = nullptr;
+    if (slr_current_device(&dev) != SLR_OK || slr_create(dev, &ctx) != SLR_OK) { set_err(err, err_len, "no GPU for the registration"); return 0; }
+    std::unique_ptr<slr_ctx, int (*)(slr_ctx *)> own(ctx, slr_destroy);
+    if (slr_pointcloud_get(ctx, pc_sum.data(), pc_count.data(), n, pts.data(), SLR_MEM_HOST) != SLR_OK) {
+        set_err(err, err_len, std::string("slr_pointcloud_get: ") + slr_last_error(ctx));
+        return 0;
+    }
+    for (size_t k = 0; k < n; k++) has[k] = pc_count[k] != 0;
+    // the target: scan 0's cloud back on the camera grid
+    const int Ht = std::min(cam_h, scan_w), Wt = std::min(cam_w, scan_h);
+    std::vector<float> tgt((size_t)Ht * Wt * 3);
+    std::vector<uint8_t> tgt_has((size_t)Ht * Wt);
+    for (int i = 0; i < Ht; i++)
+        for (int j = 0; j < Wt; j++) {
+            const size_t g = (size_t)i * Wt + j, c = (size_t)j * scan_w + i;
+            memcpy(&tgt[3 * g], &pts[3 * c], 12);
+            tgt_has[g] = has[c];
+        }
+    slr_icp_desc id = {};
+    id.W = Wt; id.H = Ht;
+    id.fx = id.fy = sr.Q.at(2, 3); id.cx = -sr.Q.at(0, 3); id.cy = -sr.Q.at(1, 3);
+    id.max_dist = max_dist; id.max_edge = max_dist;
+    id.max_iters = 30; id.stop_rot = 1e-6; id.stop_trans = 1e-4; id.min_inliers = 6;
+    std::vector<float> corr((size_t)n_scans * 12, 0.0f);
+    for (int k = 0; k < n_scans; k++) {
+        float *Tk = &corr[(size_t)k * 12];
+        Tk[0] = Tk[5] = Tk[10] = 1.0f;
+        slr_icp_result r = {};
+        int use = 1;
+        if (k > 0) {
+            const float *src = &pts[3 * cells * k];
+            const uint8_t *src_has = &has[cells * k];
+            if (slr_register_icp(ctx, &id, src, src_has, cells, tgt.data(), tgt_has.data(), nullptr, Tk, &r, SLR_MEM_HOST) != SLR_OK) {
+                set_err(err, err_len, std::string("slr_register_icp: ") + slr_last_error(ctx));
+                return 0;
+            }
+            // applied only when the loop converged and the fit at the result is no worse than at identity: the same gate keeps at
+            // least as many points, with an rms no larger.  Otherwise the scan keeps its transfer_mat (identity correction).
+            static const double I12[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+            double s0[28], s1[28];
+            uint64_t n0 = 0, n1 = 0;
+            if (slr_icp_linearize(ctx, &id, src, src_has, cells, tgt.data(), tgt_has.data(), I12, s0, &n0, SLR_MEM_HOST) != SLR_OK ||
+                slr_icp_linearize(ctx, &id, src, src_has, cells, tgt.data(), tgt_has.data(), r.T, s1, &n1, SLR_MEM_HOST) != SLR_OK) {
+                set_err(err, err_len, std::string("slr_icp_linearize: ") + slr_last_error(ctx));
+                return 0;
+            }
+            use = r.stop_reason == 1 && n1 >= n0 && n1 > 0 && (n0 == 0 || s1[27] / (double)n1 <= s0[27] / (double)n0);
+            const int sn = sn_first + k;
+            const std::string out = std::string(project) + "/reconstruction/transfer_mat" + std::to_string(sn) + ".txt";
+            float O[12];
+            if (duke_load_matrix((std::string(project) + "/scan/transfer_mat" + std::to_string(sn) + ".txt").c_str(), 3, 4, O) < 0) {
+                set_err(err, err_len, "cannot read scan/transfer_mat" + std::to_string(sn) + ".txt");
+                return 0;
+            }
+            if (use) {
+                // refined transfer_mat = correction o original (the original as the series read it: through float)
+                double Rf[12];
+                for (int row = 0; row < 3; row++)
+                    for (int col = 0; col < 4; col++) {
+                        double v = col == 3 ? r.T[4 * row + 3] : 0.0;
+                        for (int m = 0; m < 3; m++) v += r.T[4 * row + m] * (double)O[4 * m + col];
+                        Rf[4 * row + col] = v;
+                    }
+                if (!exportMat(out, Rf, 3, 4)) { set_err(err, err_len, "cannot write " + out); return 0; }
+                if (T_refined) for (int m = 0; m < 12; m++) T_refined[(size_t)k * 12 + m] = (float)Rf[m];
+            } else {
+                for (int m = 0; m < 12; m++) Tk[m] = (float)I12[m];
+                std::remove(out.c_str());                    // no refined matrix: not even one left by an earlier run
+                if (T_refined) for (int m = 0; m < 12; m++) T_refined[(size_t)k * 12 + m] = O[m];
+            }
+        } else {
+            r.T[0] = r.T[5] = r.T[10] = 1.0;
+            if (T_refined) for (int m = 0; m < 12; m++) T_refined[m] = Tk[m];
+        }
+        if (applied) applied[k] = use;
+        if (results) results[k] = r;
+    }
+    slr_fuse_desc d = {};
+    d.n_frames = n_scans; d.W = scan_w; d.H = scan_h; d.voxel = voxel; d.min_points = min_points;
+    uint32_t cap = (uint32_t)(n < (1u << 22) ? n : (1u << 22)), m = 0;
+    std::vector<float> fused;
+    std::vector<uint32_t> count;
+    for (;;) {                                           // capacity grown to the reported count on SLR_ERR_OOM
+        fused.resize((size_t)cap * 3); count.resize(cap);
+        d.max_voxels = cap;
+        uint64_t rejected = 0;
+        const int st = slr_fuse_voxels(ctx, &d, pts.data(), has.data(), nullptr, corr.data(), fused.data(), count.data(), nullptr, &m,
                                        &rejected, SLR_MEM_HOST);
         if (st == SLR_OK) break;
         if (st == SLR_ERR_OOM && cap < n && cap < (1u << 30)) {

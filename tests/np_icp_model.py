@@ -1,0 +1,222 @@
+"""NumPy restatement of the point-to-plane ICP of include/slr.h (slr_cloud_normals, slr_icp_linearize, slr_register_icp), operation
+by operation in the written order: normals are bit-exact against the GPU (every step a correctly rounded f64 operation); the
+linearisation's decisions (projection, pixel, gates) are exact too, only its f64 sums are formed in another order.  Also a ray-caster
+of an analytic scene (planes and spheres about 1 m away) onto the grid of a pinhole, the known-motion fixture of the tests."""
+import math
+
+import numpy as np
+
+F64 = np.float64
+
+
+def normals(xyz, has, max_edge):
+    """xyz [H][W][3] f32, has [H][W] -> (normals [H][W][3] f32, nvalid [H][W] u8)"""
+    H, W = has.shape
+    nrm = np.zeros((H, W, 3), np.float32)
+    nv = np.zeros((H, W), np.uint8)
+    if H < 3 or W < 3:
+        return nrm, nv
+    P = xyz.astype(F64)
+    hb = has != 0
+    c, lft, rgt, up, dn = P[1:-1, 1:-1], P[1:-1, :-2], P[1:-1, 2:], P[:-2, 1:-1], P[2:, 1:-1]
+    ok = hb[1:-1, 1:-1] & hb[1:-1, :-2] & hb[1:-1, 2:] & hb[:-2, 1:-1] & hb[2:, 1:-1]
+    e2 = max_edge * max_edge
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for X in (lft, rgt, up, dn):
+            d = X - c
+            ok &= ((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]) <= e2
+        a = rgt - lft
+        b = dn - up
+        n0 = a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1]
+        n1 = a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2]
+        n2 = a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]
+        m = np.sqrt((n0 * n0 + n1 * n1) + n2 * n2)
+        ok &= m != 0
+        n0, n1, n2 = n0 / m, n1 / m, n2 / m
+        flip = ((n0 * c[..., 0] + n1 * c[..., 1]) + n2 * c[..., 2]) > 0
+    n0, n1, n2 = np.where(flip, -n0, n0), np.where(flip, -n1, n1), np.where(flip, -n2, n2)
+    inner = np.stack([n0, n1, n2], -1).astype(np.float32)
+    nrm[1:-1, 1:-1] = np.where(ok[..., None], inner, np.float32(0))
+    nv[1:-1, 1:-1] = ok
+    return nrm, nv
+
+
+def linearize(src, src_has, dst, dst_has, nrm, nvalid, pinhole, T, max_dist):
+    """-> (sums [28] f64: 21 upper A, 6 b, e; inliers).  src [..][3] f32, src_has None or one byte per point."""
+    fx, fy, cx, cy = (float(v) for v in pinhole)
+    H, W = dst_has.shape
+    s = np.asarray(src, np.float32).reshape(-1, 3)
+    keep = np.isfinite(s).all(1)
+    if src_has is not None:
+        keep &= np.asarray(src_has).reshape(-1) != 0
+    s = s[keep].astype(F64)
+    T = np.asarray(T, F64).reshape(3, 4)
+    q = [((T[r, 0] * s[:, 0] + T[r, 1] * s[:, 1]) + T[r, 2] * s[:, 2]) + T[r, 3] for r in range(3)]
+    ok = q[2] > 0
+    q = [x[ok] for x in q]
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        u = q[0] / q[2] * fx + cx
+        v = q[1] / q[2] * fy + cy
+    jf, if_ = np.floor(u + 0.5), np.floor(v + 0.5)
+    ok = (jf >= 0) & (jf < W) & (if_ >= 0) & (if_ < H)
+    q = [x[ok] for x in q]
+    o = if_[ok].astype(np.int64) * W + jf[ok].astype(np.int64)
+    ok = (np.asarray(dst_has).reshape(-1)[o] != 0) & (np.asarray(nvalid).reshape(-1)[o] != 0)
+    q = [x[ok] for x in q]
+    o = o[ok]
+    P = np.asarray(dst, np.float32).reshape(-1, 3)[o].astype(F64)
+    d = [q[a] - P[:, a] for a in range(3)]
+    ok = ((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) <= max_dist * max_dist
+    q = [x[ok] for x in q]
+    d = [x[ok] for x in d]
+    n = np.asarray(nrm, np.float32).reshape(-1, 3)[o[ok]].astype(F64)
+    nx, ny, nz = n[:, 0], n[:, 1], n[:, 2]
+    r = (nx * d[0] + ny * d[1]) + nz * d[2]
+    J = [q[1] * nz - q[2] * ny, q[2] * nx - q[0] * nz, q[0] * ny - q[1] * nx, nx, ny, nz]
+    sums = [np.sum(J[a] * J[b]) for a in range(6) for b in range(a, 6)]
+    sums += [np.sum(J[a] * r) for a in range(6)]
+    sums.append(np.sum(r * r))
+    return np.array(sums, F64), int(len(r))
+
+
+def solve(sums):
+    """A xi = -b by Cholesky; None when A counts as singular (the pivot rule of include/slr.h)"""
+    A = np.zeros((6, 6))
+    k = 0
+    for r in range(6):
+        for c in range(r, 6):
+            A[r, c] = A[c, r] = sums[k]
+            k += 1
+    rot, tra = max(A[0, 0], A[1, 1], A[2, 2]), max(A[3, 3], A[4, 4], A[5, 5])
+    if not (rot > 0 and tra > 0 and math.isfinite(rot) and math.isfinite(tra)):
+        return None
+    L = np.zeros((6, 6))
+    for j in range(6):
+        dj = A[j, j]
+        for m in range(j):
+            dj -= L[j, m] * L[j, m]
+        if not dj > 1e-6 * (rot if j < 3 else tra):
+            return None
+        L[j, j] = math.sqrt(dj)
+        for i in range(j + 1, 6):
+            s = A[i, j]
+            for m in range(j):
+                s -= L[i, m] * L[j, m]
+            L[i, j] = s / L[j, j]
+    y = np.zeros(6)
+    for i in range(6):
+        s = -sums[21 + i]
+        for m in range(i):
+            s -= L[i, m] * y[m]
+        y[i] = s / L[i, i]
+    xi = np.zeros(6)
+    for i in range(5, -1, -1):
+        s = y[i]
+        for m in range(i + 1, 6):
+            s -= L[m, i] * xi[m]
+        xi[i] = s / L[i, i]
+    return xi
+
+
+def rodrigues(w):
+    t = math.sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2])
+    R = np.eye(3)
+    if t > 0:
+        a, h = math.sin(t) / t, math.sin(0.5 * t)
+        b = 2 * h * h / (t * t)
+        K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+        R = R + a * K + b * (K @ K)
+    return R
+
+
+def update(xi, T):
+    """[R(omega) | v] T"""
+    T = np.asarray(T, F64).reshape(3, 4)
+    R = rodrigues(xi[:3])
+    out = R @ T
+    out[:, 3] += xi[3:]
+    return out
+
+
+def register(src, src_has, dst, dst_has, pinhole, T_init=None, max_dist=20.0, max_edge=10.0, max_iters=30, stop_rot=1e-6,
+             stop_trans=1e-4, min_inliers=6):
+    """the loop of slr_register_icp -> (T [3][4] f64, {iterations, stop_reason, inliers, rms})"""
+    nrm, nv = normals(dst, dst_has, max_edge)
+    T = np.eye(3, 4) if T_init is None else np.asarray(T_init, np.float32).astype(F64).reshape(3, 4)
+    res = {"iterations": 0, "stop_reason": 2, "inliers": 0, "rms": 0.0}
+    for it in range(1, max_iters + 1):
+        sums, n_in = linearize(src, src_has, dst, dst_has, nrm, nv, pinhole, T, max_dist)
+        res["inliers"], res["rms"] = n_in, (math.sqrt(sums[27] / n_in) if n_in else 0.0)
+        if n_in < min_inliers:
+            res["stop_reason"] = 3
+            break
+        xi = solve(sums)
+        if xi is None:
+            res["stop_reason"] = 4
+            break
+        T = update(xi, T)
+        res["iterations"] = it
+        if np.linalg.norm(xi[:3]) < stop_rot and np.linalg.norm(xi[3:]) < stop_trans:
+            res["stop_reason"] = 1
+            break
+    return T, res
+
+
+# ---- fixtures -----------------------------------------------------------------------------------------------------------------------
+def axis_angle(axis, deg):
+    axis = np.asarray(axis, F64) / np.linalg.norm(axis)
+    return rodrigues(axis * math.radians(deg))
+
+
+def motion(axis=(0.3, 1.0, 0.2), deg=1.5, t=(2.0, -2.5, 2.2)):
+    """the known rigid motion of the tests: about 1.5 deg about a tilted axis and about 4 mm (|t| = 3.9)"""
+    M = np.zeros((3, 4))
+    M[:, :3] = axis_angle(axis, deg)
+    M[:, 3] = t
+    return M
+
+
+def invert(M):
+    M = np.asarray(M, F64).reshape(3, 4)
+    out = np.zeros((3, 4))
+    out[:, :3] = M[:, :3].T
+    out[:, 3] = -M[:, :3].T @ M[:, 3]
+    return out
+
+
+SCENE = ([("plane", (0.0, 0.0, -1.0), -1250.0),                   # n . X = d: a back wall at z = 1250
+          ("plane", (0.0, -1.0, 0.0), -260.0),                    # a floor below the axis at y = 260
+          ("plane", (0.8, 0.0, -0.6), -900.0)],                   # a wall at the left, tilted
+         [((-110.0, -60.0, 950.0), 130.0), ((170.0, 70.0, 1020.0), 110.0), ((40.0, -190.0, 1100.0), 90.0)])
+
+
+def render(W, H, pinhole, M=None, scene=SCENE, far=3000.0):
+    """ray-cast the scene (given in the frame of camera A) onto the pixel grid of a camera whose frame is X_B = M X_A (M None: A
+    itself) -> xyz [H][W][3] f32 in camera B's frame, has [H][W] u8"""
+    fx, fy, cx, cy = pinhole
+    M = np.eye(3, 4) if M is None else np.asarray(M, F64).reshape(3, 4)
+    R, t = M[:, :3], M[:, 3]
+    j, i = np.meshgrid(np.arange(W, dtype=F64), np.arange(H, dtype=F64))
+    dB = np.stack([(j - cx) / fx, (i - cy) / fy, np.ones_like(j)], -1).reshape(-1, 3)
+    d = dB @ R                                            # R^T dB: the rays in A's frame
+    o = -R.T @ t
+    best = np.full(len(d), np.inf)
+    planes, spheres = scene
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for _, n, c in planes:
+            n = np.asarray(n, F64)                         # unit normals
+            tt = (c - n @ o) / (d @ n)
+            best = np.where((tt > 0) & (tt < best), tt, best)
+        for cen, rad in spheres:
+            oc = o - np.asarray(cen)
+            a = np.einsum("ij,ij->i", d, d)
+            b = 2 * (d @ oc)
+            cc = oc @ oc - rad * rad
+            disc = b * b - 4 * a * cc
+            tt = (-b - np.sqrt(disc)) / (2 * a)
+            best = np.where((disc >= 0) & (tt > 0) & (tt < best), tt, best)
+    XA = o + best[:, None] * d
+    hit = np.isfinite(best) & (XA[:, 2] < far)
+    XB = XA @ R.T + t
+    xyz = np.where(hit[:, None], XB, 0.0).astype(np.float32).reshape(H, W, 3)
+    return xyz, hit.astype(np.uint8).reshape(H, W)

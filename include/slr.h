@@ -525,7 +525,8 @@ int slr_fuse_last_stats(slr_ctx *ctx, slr_fuse_stats *out);
  *           the origin looking along +z.  For a K4 cloud (slr_reconstruct_mf*, no calibration T): fx = fy = Q[2][3], cx = -Q[0][3],
  *           cy = -Q[1][3] (capi.pinhole_from_Q).
  *   source: src_xyz [n_src][3] f32 -- any point list (an organised grid flattened, or a fused cloud) -- and src_has [n_src] u8 or NULL
- *           (every point present); n_src < 2^32.
+ *           (every point present); n_src < 2^32.  n_src may be 0, and src_xyz / src_has NULL then (an empty device tensor has no
+ *           address): the sums are all zero, there are no inliers, and slr_register_icp stops with stop_reason 3 at its first linearisation.
  * Normals (slr_cloud_normals; every step f64 and correctly rounded, in exactly this order; P = the f32 point widened):
  *   pixel (i, j) has a normal iff 1 <= i < H-1, 1 <= j < W-1, has is set at (i, j), (i, j-1), (i, j+1), (i-1, j), (i+1, j), and each
  *   of those four neighbours X satisfies ((d_x d_x + d_y d_y) + d_z d_z) <= max_edge max_edge, d = X - P(i, j);

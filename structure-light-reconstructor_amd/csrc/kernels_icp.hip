@@ -20,6 +20,8 @@ constexpr int kIcpBlock = 1024;                // linearise: 16 waves, 4 per SIM
 constexpr unsigned kIcpMaxGroups = 256;        // linearise: at most one workgroup per CU; more points loop.  The reduce holds
                                                // all partials in LDS: 29 x 256 x 8 B = 58 KB
 constexpr int kIcpNormBX = 64, kIcpNormBY = 4; // normals: one wave per row segment
+// tests/np_icp_model.py (sum_depth) reads kIcpBlock and kIcpMaxGroups from this file and restates the summation tree below (grid-
+// stride loop, butterfly over 64 lanes, the waves in order, the workgroups in order) to bound the rounding error of every sum.
 
 unsigned icp_groups(size_t n_src)
 {

@@ -1866,7 +1866,7 @@ int slr_icp_linearize(slr_ctx *c, const slr_icp_desc *d, const float *src_xyz, c
                       const float *dst_xyz, const uint8_t *dst_has, const double *T, double *sums, uint64_t *inliers, slr_mem mem)
 {
     if (!c) return SLR_ERR_INVALID_ARG;
-    if (!d || !src_xyz || !dst_xyz || !dst_has || !T || !sums || !inliers) return fail(c, SLR_ERR_INVALID_ARG, "null argument");
+    if (!d || (!src_xyz && n_src) || !dst_xyz || !dst_has || !T || !sums || !inliers) return fail(c, SLR_ERR_INVALID_ARG, "null argument");
     if (mem != SLR_MEM_HOST && mem != SLR_MEM_DEVICE) return fail(c, SLR_ERR_INVALID_ARG, "bad memory kind");
     SLR_TRY(icp_check_desc(c, d));
     if (n_src >= (1ull << 32)) return fail(c, SLR_ERR_INVALID_ARG, "n_src must be < 2^32");
@@ -1883,7 +1883,7 @@ int slr_register_icp(slr_ctx *c, const slr_icp_desc *d, const float *src_xyz, co
                      const float *dst_xyz, const uint8_t *dst_has, const float *T_init, float *T_out, slr_icp_result *res, slr_mem mem)
 {
     if (!c) return SLR_ERR_INVALID_ARG;
-    if (!d || !src_xyz || !dst_xyz || !dst_has || !T_out || !res) return fail(c, SLR_ERR_INVALID_ARG, "null argument");
+    if (!d || (!src_xyz && n_src) || !dst_xyz || !dst_has || !T_out || !res) return fail(c, SLR_ERR_INVALID_ARG, "null argument");
     if (mem != SLR_MEM_HOST && mem != SLR_MEM_DEVICE) return fail(c, SLR_ERR_INVALID_ARG, "bad memory kind");
     SLR_TRY(icp_check_desc(c, d));
     if (n_src >= (1ull << 32)) return fail(c, SLR_ERR_INVALID_ARG, "n_src must be < 2^32");

@@ -1,5 +1,6 @@
 """Point-to-plane ICP on the MI355X (slr_cloud_normals, slr_icp_linearize, slr_register_icp) against the NumPy model
-(tests/np_icp_model.py): normals bit for bit, a bench-sized linearisation with the model's exact inlier count and its sums to 1e-9,
+(tests/np_icp_model.py): normals bit for bit, a bench-sized linearisation with the model's exact inlier count, its sums to 1e-9 and
+each within the rounding bound of the kernel's summation tree,
 a known motion recovered, a verged-rig frame registered back onto itself, bit-identical results across calls and memory kinds,
 stop reason 3, and argument checks.  Output and scratch poisoning are on (tests/conftest.py)."""
 import ctypes as C
@@ -14,10 +15,10 @@ from util import bits_equal, np_of
 
 pytestmark = pytest.mark.gpu
 
-# Time limits per test, sized to each case on an MI355X (the bench-sized case renders and models 12 M points on the host).  SIGALRM
-# ends a test between Python statements only; every kernel of kernels_icp.hip is a bounded loop, and the suite runs under an outer
-# time limit as well.
-LIMITS_S = {"test_normals_match_the_model_bit_for_bit": 60, "test_linearize_at_bench_size_matches_the_model": 240,
+# Time limits per test, sized to each case on an MI355X (the bench-sized case renders and models 12 M points on the host, and sums
+# 2 x 28 x 12 M terms exactly).  SIGALRM ends a test between Python statements only; every kernel of kernels_icp.hip is a bounded
+# loop, and the suite runs under an outer time limit as well.
+LIMITS_S = {"test_normals_match_the_model_bit_for_bit": 60, "test_linearize_at_bench_size_matches_the_model": 360,
             "test_register_recovers_a_known_motion": 120, "test_verged_frame_registers_onto_itself": 120,
             "test_bit_identical_across_calls_and_memory_kinds": 120, "test_too_few_inliers_stops_with_reason_3": 60,
             "test_invalid_arguments_are_refused_before_any_work": 30}
@@ -97,6 +98,11 @@ def test_linearize_at_bench_size_matches_the_model(ctx, bench_pair):
         gs, gn = ctx.icp_linearize(sx, sh if has is not None else None, dx, dh, ph, T, 30.0, 10.0)
         assert gn == en and en > 0.5 * xa.shape[0] * xa.shape[1], (gn, en)
         assert np.abs(gs - es).max() <= 1e-9 * np.abs(es).max(), np.abs(gs - es).max() / np.abs(es).max()
+        # and each entry on its own, within the rounding bound of the kernel's summation tree around the exactly rounded sum
+        terms, tn = M.linearize_terms(xb, has, xa, ha, nrm, nv, ph, T, 30.0)
+        assert tn == en
+        M.assert_within_rounding_bound(gs, terms, xb.shape[0] * xb.shape[1])
+        del terms
 
 
 def test_register_recovers_a_known_motion(ctx):

@@ -1,7 +1,9 @@
 """No-GPU checks of the point-to-plane ICP model (tests/np_icp_model.py, the rule of include/slr.h) and of capi.pinhole_from_Q:
 a known motion between two noise-free ray-cast renders is recovered, a planar scene is refused as singular, and the pinhole read off
-Q sends the points the CPU oracle's K4 triangulates back to their own grid pixels."""
+Q sends the points the CPU oracle's K4 triangulates back to their own grid pixels.  Also the exact references the GPU tests lean on
+(tests/test_gpu_icp_exact.py): the wall fixture's closed form, sum_depth, linearize_terms, update_exact and the rational solve."""
 import importlib
+import math
 
 import numpy as np
 
@@ -87,3 +89,81 @@ def test_pinhole_from_Q_maps_k4_points_to_their_pixels(oracle):
     u, v = p[:, 0] / p[:, 2] * fx + cx, p[:, 1] / p[:, 2] * fy + cy
     assert np.abs(u - j).max() < 1.0 and np.abs(v - i).max() < 1.0
     assert (np.floor(u + 0.5) == j).mean() > 0.99 and (np.floor(v + 0.5) == i).mean() > 0.99
+
+
+def test_wall_closed_form_equals_the_model_bit_for_bit():
+    """the exact-sum fixture: every off-border point kept, the int64 closed form equal to linearize and to linearize_terms"""
+    W, H = 1024, 768
+    xyz, has, ph = M.wall_target(W, H)
+    nrm, nv = M.normals(xyz, has, 10.0)
+    assert int(nv.sum()) == (W - 2) * (H - 2) and (nrm[nv == 1] == np.float32([0, 0, -1])).all()
+    rng = np.random.default_rng(11)
+    n = 200000
+    pi, pj, dl = rng.integers(0, H, n), rng.integers(0, W, n), rng.integers(-3, 4, n)
+    src = M.wall_source(W, H, pi, pj, dl)
+    src_has = rng.integers(0, 4, n).astype(np.uint8) * 60                  # 0, 60, 120, 180: holes and bytes other than 1
+    keep = (pi > 0) & (pi < H - 1) & (pj > 0) & (pj < W - 1) & (src_has != 0) & (np.abs(dl) <= 2)
+    cs, cn, mag = M.wall_sums(src, keep)
+    assert (mag > 0).sum() == 10 and cn > 0.3 * n
+    es, en = M.linearize(src, src_has, xyz, has, nrm, nv, ph, np.eye(3, 4), 0.25)
+    assert en == cn and np.array_equal(es, cs), np.nonzero(es != cs)
+    terms, tn = M.linearize_terms(src, src_has, xyz, has, nrm, nv, ph, np.eye(3, 4), 0.25)
+    assert tn == en and len(terms) == 28
+    assert all(math.fsum(t) == c and np.sum(t) == e for t, c, e in zip(terms, cs, es))
+
+
+def test_linearize_terms_sum_to_linearize():
+    ph = (1.0 * W, 1.1 * W, 0.5 * W + 0.3, 0.5 * H - 0.4)
+    xa, ha = M.render(W, H, ph)
+    xb, hb = M.render(W, H, ph, M.motion())
+    nrm, nv = M.normals(xa, ha, 10.0)
+    T = M.invert(M.motion(deg=1.2, t=(1.5, -2.0, 1.0)))
+    es, en = M.linearize(xb, hb, xa, ha, nrm, nv, ph, T, 30.0)
+    terms, tn = M.linearize_terms(xb, hb, xa, ha, nrm, nv, ph, T, 30.0)
+    assert tn == en > 0.5 * W * H
+    assert all(np.array_equal(np.sum(t), e) for t, e in zip(terms, es))
+
+
+def test_sum_depth_follows_the_kernel_constants():
+    block, groups = M._kernel_constants()
+    assert (block, groups) == (1024, 256)
+    want = {1: 23, 63: 23, 64: 23, 65: 23, 1023: 23, 1024: 23, 1025: 24, 262143: 278, 262144: 278, 262145: 279,
+            5 * 262144 + 777: 283, 4096 * 3000: 324, 0: 0}
+    assert {n: M.sum_depth(n) for n in want} == want
+
+
+def test_swapped_focal_lengths_change_the_count():
+    """every other ICP fixture has fx == fy; on an anisotropic pinhole the two focal lengths are not interchangeable"""
+    Wa, Ha = 1024, 768
+    ph = (1.0 * Wa, 1.1 * Wa, 0.5 * Wa + 0.3, 0.5 * Ha - 0.4)
+    xa, ha = M.render(Wa, Ha, ph)
+    xb, hb = M.render(Wa, Ha, ph, M.motion())
+    nrm, nv = M.normals(xa, ha, 10.0)
+    T = M.invert(M.motion(deg=1.2, t=(1.5, -2.0, 1.0)))
+    n_ok = M.linearize(xb, hb, xa, ha, nrm, nv, ph, T, 30.0)[1]
+    n_sw = M.linearize(xb, hb, xa, ha, nrm, nv, (ph[1], ph[0], ph[2], ph[3]), T, 30.0)[1]
+    assert n_ok > 0.6 * Wa * Ha and n_sw < 0.5 * n_ok, (n_ok, n_sw)
+
+
+def test_rational_solve_agrees_with_solve():
+    ph = (1.0 * W, 1.1 * W, 0.5 * W + 0.3, 0.5 * H - 0.4)
+    xa, ha = M.render(W, H, ph)
+    nrm, nv = M.normals(xa, ha, 10.0)
+    for k in range(4):
+        xb, hb = M.render(W, H, ph, M.motion(deg=0.5 + k, t=(k, -2.5, 1.0)))
+        sums, _ = M.linearize(xb, hb, xa, ha, nrm, nv, ph, np.eye(3, 4), 40.0)
+        err, kappa = M.solve_error(sums, M.solve(sums))
+        assert kappa < 100 and err <= 8 * kappa * 2.0 ** -53, (err, kappa)
+    # a plane leaves A singular in exact arithmetic up to the f32 noise of its normals: both solvers see it
+    xp, hp = M.render(W, H, ph, scene=([("plane", (0.0, 0.0, -1.0), -1000.0)], []))
+    sums, _ = M.linearize(xp, hp, xp, hp, *M.normals(xp, hp, 10.0), ph, np.eye(3, 4), 40.0)
+    assert M.solve(sums) is None
+
+
+def test_update_exact_agrees_with_update():
+    rng = np.random.default_rng(3)
+    for _ in range(20):
+        xi = np.concatenate([rng.normal(0, 0.05, 3), rng.normal(0, 5, 3)])
+        T = M.motion(axis=rng.normal(size=3), deg=rng.uniform(0, 10), t=rng.normal(0, 10, 3))
+        assert np.abs(M.update_exact(xi, T) - M.update(xi, T)).max() <= 1e-15 * max(1.0, np.abs(T).max())
+    assert np.array_equal(M.update_exact(np.zeros(6), T), T)
